@@ -12,6 +12,14 @@ driver launches it under torch.distributed.run with one rank per GPU over
 RCCL.  W untimed warmup steps, then exactly K timed steps bracketed by
 barrier + torch.cuda.synchronize on both sides; elapsed time is the MAX
 over ranks; rank 0 prints one JSON line.
+
+A plain run does only that: set up, warm up, time the K steps, print the
+line.  ``--dump-outputs DIR`` additionally writes what the last timed step
+computed (see ``dump_outputs``) so two builds can be compared output for
+output; inputs and initial weights are seeded, hence identical from run to
+run.  ``--full`` is where measurements beyond the headline figure belong
+(CPU baselines, other precisions or sizes, per-kernel figures); this
+benchmark has none of its own, so today the flag adds nothing.
 """
 from __future__ import annotations
 
@@ -66,7 +74,39 @@ def parse_args():
                    help="benchmark config (BASELINE.json); headline = toy_net")
     p.add_argument("--no-h2d", action="store_true",
                    help="skip the per-step H2D copy (ablation only)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the last step's loss, "
+                        "logits and the updated parameters as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline "
+                        "figure (none today)")
     return p.parse_args()
+
+
+# --dump-outputs budget: 64 MB in all.  Logits are ≤ 4096×10 or 1024×1000
+# fp32 (≤ 4 MB) and are written whole; the flattened parameters are written
+# whole up to 8M elements (32 MB) and as a fixed seeded sample beyond that
+# (resnet50 has 25.6M, vgg16 138M).
+DUMP_PARAM_ELEMS = 8 * 1024 * 1024
+
+
+def dump_outputs(out_dir, loss, logits, model):
+    """Write what one training step hands back to its caller — the batch
+    loss, the logits, and (as the step's side effect) the updated model
+    parameters — as float32 .npy files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"),
+            loss.detach().float().cpu().numpy())
+    np.save(os.path.join(out_dir, "logits.npy"),
+            logits.detach().float().cpu().numpy())
+    flat = torch.cat([p.detach().float().reshape(-1).cpu()
+                      for p in model.parameters()])
+    if flat.numel() > DUMP_PARAM_ELEMS:
+        g = torch.Generator().manual_seed(2024)
+        idx = torch.randperm(flat.numel(), generator=g)[:DUMP_PARAM_ELEMS]
+        flat = flat[idx.sort().values]
+    np.save(os.path.join(out_dir, "params.npy"), flat.numpy())
 
 
 class SyntheticData:
@@ -94,11 +134,19 @@ class SyntheticData:
             self.host_targets.append(tgt)
         if self.h2d:
             self.copy_stream = torch.cuda.Stream(device=device)
+            # One device slot per host buffer, so host buffer k always lands
+            # in device slot k.  The host runs ahead of the device, and the
+            # copy stream does not wait for the step that last read a slot;
+            # with fewer slots than buffers a refill could replace a batch
+            # under a step still reading it and the run was not repeatable.
+            # Now a refill rewrites the bytes the slot already holds, so what
+            # a step reads no longer depends on that timing — at no cost in
+            # synchronisation, and with the same H2D traffic per step.
             self.dev_images = [torch.empty_like(i, device=device)
-                               for i in self.host_images[:2]]
+                               for i in self.host_images]
             self.dev_targets = [torch.empty_like(t, device=device)
-                                for t in self.host_targets[:2]]
-            self.events = [torch.cuda.Event(), torch.cuda.Event()]
+                                for t in self.host_targets]
+            self.events = [torch.cuda.Event() for _ in self.host_images]
             self._i = 0
             self._prefetch(0)
         else:
@@ -119,10 +167,11 @@ class SyntheticData:
             j = self._i % len(self.dev_images)
             self._i += 1
             return self.dev_images[j], self.dev_targets[j]
-        slot = (self._i - 1) % 2
+        n = len(self.dev_images)
+        slot = (self._i - 1) % n
         torch.cuda.current_stream(self.device).wait_event(self.events[slot])
         img, tgt = self.dev_images[slot], self.dev_targets[slot]
-        self._prefetch(slot ^ 1)
+        self._prefetch((slot + 1) % n)
         return img, tgt
 
 
@@ -169,10 +218,11 @@ def main():
         with amp.scale_loss(batch_loss, apex_optimizer) as scaled_loss:
             scaled_loss.backward()
         apex_optimizer.step()
-        return batch_loss
+        return batch_loss, outputs
 
+    last = None
     for _ in range(args.warmup):
-        step()
+        last = step()
 
     if use_cuda:
         torch.cuda.synchronize()
@@ -181,7 +231,7 @@ def main():
         torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     if use_cuda:
         torch.cuda.synchronize()
     dist.barrier()
@@ -193,6 +243,9 @@ def main():
                      device=device if backend == "nccl" else "cpu")
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+
+    if rank == 0 and args.dump_outputs and last is not None:
+        dump_outputs(args.dump_outputs, last[0], last[1], model)
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1000.0

@@ -46,6 +46,10 @@ def _find_idx(root: str, base: str) -> Optional[str]:
     return None
 
 
+def _offline() -> bool:
+    return os.environ.get("DDPX_OFFLINE", "0") == "1"
+
+
 _MNIST_MIRRORS = (
     "https://ossci-datasets.s3.amazonaws.com/mnist/",
     "http://yann.lecun.com/exdb/mnist/",
@@ -56,7 +60,10 @@ def _download_mnist(root: str, bases) -> None:
     """Best-effort fetch of the raw IDX .gz files (reference parity:
     torchvision download=True at reference utils/train.py:25).  In the
     offline build/test environment this fails fast and the caller falls
-    back to local files / synthetic data."""
+    back to local files / synthetic data.  DDPX_OFFLINE=1 skips the attempt
+    (and the directory it would create) altogether — the test suite sets it."""
+    if _offline():
+        return
     import urllib.error
     import urllib.request
     dest = os.path.join(root, "MNIST", "raw")
@@ -142,6 +149,8 @@ class CIFAR10(Dataset):
     def _download(root: str) -> None:
         """Best-effort fetch+extract of the python-batches tarball
         (torchvision download=True parity; offline → warn and fall back)."""
+        if _offline():
+            return
         import tarfile
         import urllib.error
         import urllib.request

@@ -8,6 +8,12 @@ REPO_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO_ROOT not in sys.path:
     sys.path.insert(0, REPO_ROOT)
 
+# The suite is self-contained: train(args) asks its datasets for
+# download=True, which must neither reach for the network nor create
+# directories outside the test's tmp_path.  Set in os.environ (not a
+# fixture) so that the subprocesses the tests start inherit it.
+os.environ["DDPX_OFFLINE"] = "1"
+
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs an MI355X GPU (run with -m gpu)")

@@ -45,6 +45,43 @@ def test_bench_json_contract():
 
 
 @pytest.mark.timeout(300)
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the last timed step's loss/logits/parameters as
+    float32 .npy; same arguments => same inputs => identical files.  The
+    second run also passes --full, which must not change the headline path."""
+    import numpy as np
+    env = dict(os.environ)
+    env.update({"MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29679",
+                "DDPX_NO_TQDM": "1"})
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        out = subprocess.run(
+            [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1",
+             "--steps", "3", "--warmup", "1", "--batch-size", "8",
+             "--dump-outputs", str(d)] + extra,
+            env=env, cwd=REPO, capture_output=True, text=True, timeout=280)
+        assert out.returncode == 0, out.stderr[-2000:]
+        json_lines = [ln for ln in out.stdout.splitlines()
+                      if ln.startswith("{")]
+        assert len(json_lines) == 1, out.stdout
+        rec = json.loads(json_lines[0])
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+        assert sorted(os.listdir(d)) == ["logits.npy", "loss.npy",
+                                         "params.npy"]
+        dumps.append({f: np.load(d / f) for f in os.listdir(d)})
+    a, b = dumps
+    assert a["logits.npy"].shape == (8, 10) and a["loss.npy"].shape == ()
+    n_params = a["params.npy"].size
+    assert a["params.npy"].ndim == 1 and n_params > 1000
+    for f in a:
+        assert a[f].dtype == np.float32, f
+        assert np.isfinite(a[f]).all(), f
+        assert np.array_equal(a[f], b[f]), f
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2 ** 20
+
+
+@pytest.mark.timeout(300)
 def test_bench_world2_rank0_prints_once():
     """The driver's N>1 launch shape: one process per rank with
     RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* env — only rank 0 prints the JSON

@@ -86,7 +86,7 @@ def test_train_e2e_gpu(tmp_path, monkeypatch):
     args = types.SimpleNamespace(
         exp_name="GPU_run", learning_rate=0.1, batch_size=512, epochs=2,
         warmup_epochs=1, warmup_type="linear", seed_num=42,
-        data_path="/nonexistent", model_path=str(tmp_path), local_rank=0)
+        data_path=str(tmp_path / "no_data"),model_path=str(tmp_path), local_rank=0)
     train(args)
     assert os.path.exists(os.path.join(tmp_path, "GPU_run.pt"))
     dist.destroy_process_group()

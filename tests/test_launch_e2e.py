@@ -21,8 +21,8 @@ def test_launch_world2_trains_in_lockstep(tmp_path):
     out = subprocess.run(
         [sys.executable, "-m", "ddp_tricks_amd.launch",
          "--nproc_per_node=2", "--master_port=29699", "run.py",
-         "-n=L2E", "-e=2", "-w=1", "-b=64", "-d=/nonexistent",
-         f"-p={tmp_path}"],
+         "-n=L2E", "-e=2", "-w=1", "-b=64",
+         f"-d={tmp_path / 'no_data'}", f"-p={tmp_path}"],
         env=env, cwd=REPO, capture_output=True, text=True, timeout=280)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("epoch:")]

@@ -95,7 +95,7 @@ def test_train_resnet18_cifar10_cpu(tmp_path, monkeypatch):
     args = types.SimpleNamespace(
         exp_name="R18", learning_rate=0.05, batch_size=64, epochs=1,
         warmup_epochs=1, warmup_type="linear", seed_num=42,
-        data_path="/nonexistent", model_path=str(tmp_path), local_rank=0,
+        data_path=str(tmp_path / "no_data"),model_path=str(tmp_path), local_rank=0,
         model="resnet18", dataset="cifar10")
     train(args)
     import torch

@@ -15,7 +15,7 @@ def _args(tmp_path, epochs, resume):
     return types.SimpleNamespace(
         exp_name="RES", learning_rate=0.05, batch_size=64, epochs=epochs,
         warmup_epochs=2, warmup_type="linear", seed_num=42,
-        data_path="/nonexistent", model_path=str(tmp_path), local_rank=0,
+        data_path=str(tmp_path / "no_data"),model_path=str(tmp_path), local_rank=0,
         resume=resume)
 
 

@@ -21,7 +21,7 @@ def _args(tmp_path, **over):
     a = types.SimpleNamespace(
         exp_name="TEST_run", learning_rate=0.1, batch_size=64, epochs=3,
         warmup_epochs=2, warmup_type="linear", seed_num=42,
-        data_path="/nonexistent_data", model_path=str(tmp_path),
+        data_path=str(tmp_path / "no_data"), model_path=str(tmp_path),
         local_rank=0)
     for k, v in over.items():
         setattr(a, k, v)
@@ -80,13 +80,13 @@ def test_validate_tool(tmp_path, monkeypatch):
     args = types.SimpleNamespace(
         exp_name="VAL", learning_rate=0.05, batch_size=64, epochs=1,
         warmup_epochs=1, warmup_type="linear", seed_num=42,
-        data_path="/nonexistent", model_path=str(tmp_path), local_rank=0)
+        data_path=str(tmp_path / "no_data"),model_path=str(tmp_path), local_rank=0)
     train(args)
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, DDPX_SYNTH_SAMPLES="256")
     r = subprocess.run(
         [sys.executable, os.path.join(repo, "tools", "validate.py"),
-         "-n", "VAL", "-p", str(tmp_path), "-d", "/nonexistent"],
+         "-n", "VAL", "-p", str(tmp_path), "-d", str(tmp_path / "no_data")],
         capture_output=True, text=True, timeout=300, env=env, cwd=repo)
     assert r.returncode == 0, r.stderr
     assert "valid_acc" in r.stdout
@@ -113,7 +113,7 @@ def test_two_runs_same_seed_identical(tmp_path, monkeypatch):
         a = types.SimpleNamespace(
             exp_name=f"DET{run}", learning_rate=0.1, batch_size=64, epochs=2,
             warmup_epochs=1, warmup_type="linear", seed_num=42,
-            data_path="/nonexistent", model_path=str(tmp_path), local_rank=0,
+            data_path=str(tmp_path / "no_data"),model_path=str(tmp_path), local_rank=0,
             resume=True)
         train(a)
         sds.append(torch.load(os.path.join(tmp_path, f"DET{run}.resume.pt"),
