@@ -50,14 +50,14 @@ class Toy_Net(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         # walk the Sequentials explicitly so each conv->BN pair runs the
-        # fused stats path (parameter keys are unchanged — same children)
+        # fused stats path (parameter keys are unchanged — same children);
+        # the two BN->MaxPool junctions hand their pool to conv_bn, which
+        # runs BN+ReLU+pool as one op on the GPU training path
         from ..ops.functional import conv_bn
         c = self.conv
         out = conv_bn(c[0], c[1], x)
-        out = conv_bn(c[3], c[4], out)
-        out = c[6](out)
+        out = conv_bn(c[3], c[4], out, pool=c[6])
         out = conv_bn(c[7], c[8], out)
-        out = conv_bn(c[10], c[11], out)
-        out = c[13](out)
+        out = conv_bn(c[10], c[11], out, pool=c[13])
         out = self.dense(out)
         return out

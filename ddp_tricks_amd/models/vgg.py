@@ -73,8 +73,14 @@ class VGG16BN(nn.Module):
         i = 0
         while i < len(f):
             if isinstance(f[i], Conv2d):
-                x = conv_bn(f[i], f[i + 1], x)
-                i += 3
+                # conv, BN, ReLU slot; a MaxPool2d right behind them goes
+                # along so the BN->pool junction can run fused
+                if i + 3 < len(f) and isinstance(f[i + 3], MaxPool2d):
+                    x = conv_bn(f[i], f[i + 1], x, pool=f[i + 3])
+                    i += 4
+                else:
+                    x = conv_bn(f[i], f[i + 1], x)
+                    i += 3
             else:
                 x = f[i](x)
                 i += 1

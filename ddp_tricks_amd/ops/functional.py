@@ -474,6 +474,84 @@ def batch_norm(x, running_mean, running_var, weight, bias,
     return y.to(x.dtype) if x.is_cuda and amp_mod.is_enabled() else y
 
 
+class _HIPBatchNormReluPool2(torch.autograd.Function):
+    """Training BatchNorm2d + fused ReLU + MaxPool2d(2) as one op.
+
+    The forward writes only the pooled activation and one code byte per
+    pooled element (window argmax + the winner's relu bit); the backward
+    rebuilds the full-resolution dy_eff from the pooled dy and the code.
+    Neither the full-resolution y, its relu mask nor its gradient is ever
+    materialised.  Pooled y is bit-identical to batch_norm(fuse_relu) ->
+    max_pool2d(2)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var,
+                momentum, eps, pre_stats=None):
+        ext = require_ext_for(x)
+        xb = _chlast(_to_bf16(x))
+        y, save_mean, save_invstd, code = ext.bn_fwd_train_pool2(
+            xb, weight.detach(), bias.detach(), running_mean, running_var,
+            momentum, eps, pre_stats)
+        ctx.save_for_backward(xb, weight, save_mean, save_invstd, code)
+        ctx.x_dtype = x.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xb, weight, save_mean, save_invstd, code = ctx.saved_tensors
+        ext = require_ext_for(dy)
+        dx, dweight, dbias = ext.bn_bwd_pool2(
+            xb, _chlast(_to_bf16(dy)), weight.detach(), save_mean,
+            save_invstd, code)
+        if ctx.x_dtype == torch.float32:
+            dx = dx.float()
+        return dx, dweight, dbias, None, None, None, None, None
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def _bn_pool_fusable(bn_mod, pool_mod, x) -> bool:
+    """True when bn_mod(x) -> pool_mod may run as the fused
+    BN+ReLU+pool2 kernels: training BN2d with fused ReLU feeding a plain
+    2x2/stride-2 max-pool over even extents, with no opt-in that needs the
+    full-resolution activation."""
+    if os.environ.get("DDPX_BNPOOL", "1") == "0":
+        return False
+    if (os.environ.get("DDPX_BN1PASS", "0") == "1"
+            or os.environ.get("DDPX_BNFUSE", "0") == "1"):
+        return False
+    if not (x.is_cuda and x.dim() == 4 and require_ext_for(x) is not None):
+        return False
+    if not (bn_mod.training and getattr(bn_mod, "fuse_relu", False)
+            and bn_mod.track_running_stats and bn_mod.weight is not None
+            and bn_mod.bias is not None):
+        return False
+    C, H, W = x.shape[1], x.shape[2], x.shape[3]
+    if C % 8 != 0 or C // 8 > 256 or H % 2 != 0 or W % 2 != 0:
+        return False
+    stride = pool_mod.stride if pool_mod.stride is not None \
+        else pool_mod.kernel_size
+    return (isinstance(pool_mod, torch.nn.MaxPool2d)
+            and _pair(pool_mod.kernel_size) == (2, 2)
+            and _pair(stride) == (2, 2)
+            and _pair(pool_mod.padding) == (0, 0)
+            and _pair(pool_mod.dilation) == (1, 1)
+            and not pool_mod.ceil_mode and not pool_mod.return_indices)
+
+
+def _bn_relu_pool2(bn_mod, x, pre_stats=None):
+    """The fused junction, with the module bookkeeping _bn_forward does."""
+    bn_mod._check_input_dim(x)
+    if bn_mod.num_batches_tracked is not None:
+        bn_mod.num_batches_tracked.add_(1)
+    momentum = bn_mod.momentum if bn_mod.momentum is not None else 0.1
+    return _HIPBatchNormReluPool2.apply(
+        x, bn_mod.weight, bn_mod.bias, bn_mod.running_mean,
+        bn_mod.running_var, momentum, bn_mod.eps, pre_stats)
+
+
 # ---------------------------------------------------------------- pooling ---
 
 class _HIPMaxPool2x2(torch.autograd.Function):
@@ -522,7 +600,10 @@ def max_pool2d(x, kernel_size=2, stride=None, padding=0):
     st = st[0] if isinstance(st, (tuple, list)) else st
     pad = padding[0] if isinstance(padding, (tuple, list)) else padding
     if x.is_cuda and require_ext_for(x) is not None:
-        if ks == 2 and st == 2 and pad == 0:
+        # the dedicated 2x2 kernels need even extents; an odd last row or
+        # column (dropped by floor-mode pooling) goes to the general kernel
+        if (ks == 2 and st == 2 and pad == 0
+                and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0):
             return _HIPMaxPool2x2.apply(x)
         return _HIPMaxPool.apply(x, ks, st, pad)
     return F.max_pool2d(x, kernel_size, stride, padding)
@@ -615,14 +696,20 @@ def argmax_correct(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     return (torch.argmax(logits, dim=1) == target).sum()
 
 
-def conv_bn(conv_mod, bn_mod, x, residual=None):
+def conv_bn(conv_mod, bn_mod, x, residual=None, pool=None):
     """Fused producer/consumer: on the GPU training path the conv epilogue
     emits the BN's per-channel partial statistics, and the BN forward skips
     its stats pass (SURVEY §7 M5 fusion note).  Falls back to the plain
-    composition on CPU, in eval mode, or off the MFMA path."""
+    composition on CPU, in eval mode, or off the MFMA path.
+
+    pool: the MaxPool2d module that consumes the BN output, if any.  A
+    training BN(fuse_relu) -> MaxPool2d(2) junction over even extents runs
+    as the fused BN+ReLU+pool2 kernels (``DDPX_BNPOOL=0`` opts out);
+    anything else is exactly ``pool(bn(conv(x)))``."""
     use_stats = (x.is_cuda and require_ext_for(x) is not None
                  and bn_mod.training and getattr(conv_mod, "dilation",
                                                  (1, 1)) in ((1, 1), 1))
+    stats = None
     if use_stats:
         stride = conv_mod.stride[0] if isinstance(conv_mod.stride, tuple) \
             else conv_mod.stride
@@ -630,5 +717,13 @@ def conv_bn(conv_mod, bn_mod, x, residual=None):
             else conv_mod.padding
         y, stats = _HIPConv2dStats.apply(x, conv_mod.weight, conv_mod.bias,
                                          stride, padding)
-        return bn_mod(y, residual=residual, pre_stats=stats)
-    return bn_mod(conv_mod(x), residual=residual)
+    else:
+        y = conv_mod(x)
+    if (pool is not None and residual is None
+            and _bn_pool_fusable(bn_mod, pool, y)):
+        return _bn_relu_pool2(bn_mod, y, stats)
+    if use_stats:
+        out = bn_mod(y, residual=residual, pre_stats=stats)
+    else:
+        out = bn_mod(y, residual=residual)
+    return out if pool is None else pool(out)

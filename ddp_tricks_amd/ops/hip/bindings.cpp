@@ -54,6 +54,15 @@ std::vector<at::Tensor> bn_bwd(at::Tensor x, at::Tensor dy, at::Tensor gamma,
                                bool want_dresid,
                                c10::optional<at::Tensor> pre_slab,
                                bool eval_stats);
+std::vector<at::Tensor> bn_fwd_train_pool2(at::Tensor x, at::Tensor gamma,
+                                           at::Tensor beta,
+                                           at::Tensor running_mean,
+                                           at::Tensor running_var,
+                                           double momentum, double eps,
+                                           c10::optional<at::Tensor> pre_stats);
+std::vector<at::Tensor> bn_bwd_pool2(at::Tensor x, at::Tensor dy_pooled,
+                                     at::Tensor gamma, at::Tensor save_mean,
+                                     at::Tensor save_invstd, at::Tensor code);
 
 // gemm.hip
 at::Tensor gemm_tn(at::Tensor A, at::Tensor B, c10::optional<at::Tensor> bias,
@@ -130,6 +139,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("x"), py::arg("gamma"), py::arg("beta"),
           py::arg("running_mean"), py::arg("running_var"), py::arg("eps"),
           py::arg("fuse_relu") = false, py::arg("residual") = c10::nullopt);
+    m.def("bn_fwd_train_pool2", &bn_fwd_train_pool2,
+          "BN(train) + ReLU + 2x2/s2 max-pool in one apply pass",
+          py::arg("x"), py::arg("gamma"), py::arg("beta"),
+          py::arg("running_mean"), py::arg("running_var"), py::arg("momentum"),
+          py::arg("eps"), py::arg("pre_stats") = c10::nullopt);
+    m.def("bn_bwd_pool2", &bn_bwd_pool2,
+          py::arg("x"), py::arg("dy_pooled"), py::arg("gamma"),
+          py::arg("save_mean"), py::arg("save_invstd"), py::arg("code"));
     m.def("gemm_tn", &gemm_tn, py::arg("A"), py::arg("B"),
           py::arg("bias") = c10::nullopt, py::arg("out_f32") = false);
     m.def("transpose_bf16", &transpose_bf16);

@@ -354,6 +354,207 @@ __global__ void k_bn_bwd_dx(const bf16* __restrict__ x,
     }
 }
 
+// ------------------------------------ BN + ReLU + 2x2/s2 max-pool, fused ---
+//
+// At a BatchNorm(fuse_relu) -> MaxPool2d(2) junction the full-resolution
+// activation y and its gradient are written only to be read straight back
+// by the pool kernels.  The fused trio below never materialises either:
+// the forward writes the POOLED y plus one code byte per pooled element
+// (bits 0-1: window argmax, bit 2: the winner's pre-rounding f > 0 — the
+// bit k_bn_apply_v8 would have put in its mask); the backward kernels read
+// the pooled dy + code and rebuild dy_eff per window position on the fly.
+// The forward repeats k_bn_apply_v8's arithmetic and k_maxpool2x2_fwd's
+// strict-> scan over the ROUNDED values, so pooled y and argmax are
+// bit-identical to the unfused pair.  H and W must be even.
+
+// Full-resolution row index of a pooled row's window origin.  With
+// pr = (n*Ho + ho)*Wo + wo and t = pr / Wo = n*Ho + ho, the origin row is
+// (n*H + 2ho)*W + 2wo = 4*t*Wo + 2*wo = 2*pr + 2*t*Wo.
+DEV_INLINE long pool2_origin(unsigned pr, FastDiv wo_div) {
+    unsigned t = fd_div(pr, wo_div);
+    return 2l * pr + 2l * t * wo_div.d;
+}
+
+// one thread per (n, ho, wo, 8-channel group): 4×16 B window loads,
+// 16 B pooled store, 8 B packed code
+__global__ void k_bn_apply_pool2_v8(const bf16* __restrict__ x,
+                                    bf16* __restrict__ y,
+                                    unsigned char* __restrict__ code,
+                                    const float* __restrict__ scale,
+                                    const float* __restrict__ shift,
+                                    long total_v, int Cv, int W,
+                                    FastDiv cv_div, FastDiv wo_div) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total_v) return;
+    unsigned pr = fd_div((unsigned)i, cv_div);
+    int c8 = (int)fd_mod((unsigned)i, cv_div, pr);
+    const s16x8* base = reinterpret_cast<const s16x8*>(
+        x + pool2_origin(pr, wo_div) * (Cv * 8)) + c8;
+    const int wv = W * Cv;
+    s16x8 v0 = base[0];
+    s16x8 v1 = base[Cv];
+    s16x8 v2 = base[wv];
+    s16x8 v3 = base[wv + Cv];
+    const int cv = c8 * 8;
+    s16x8 o;
+    unsigned long long packed = 0;
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float sc = scale[cv + j], sh = shift[cv + j];
+        float f0 = fmaf(us2f((unsigned short)v0[j]), sc, sh);
+        float f1 = fmaf(us2f((unsigned short)v1[j]), sc, sh);
+        float f2 = fmaf(us2f((unsigned short)v2[j]), sc, sh);
+        float f3 = fmaf(us2f((unsigned short)v3[j]), sc, sh);
+        unsigned short u0 = f2us(fmaxf(f0, 0.f));
+        unsigned short u1 = f2us(fmaxf(f1, 0.f));
+        unsigned short u2 = f2us(fmaxf(f2, 0.f));
+        unsigned short u3 = f2us(fmaxf(f3, 0.f));
+        float b = us2f(u0);
+        unsigned short ub = u0;
+        unsigned cd = f0 > 0.f ? 4u : 0u;
+        float r1 = us2f(u1);
+        if (r1 > b) { b = r1; ub = u1; cd = f1 > 0.f ? 5u : 1u; }
+        float r2 = us2f(u2);
+        if (r2 > b) { b = r2; ub = u2; cd = f2 > 0.f ? 6u : 2u; }
+        float r3 = us2f(u3);
+        if (r3 > b) { b = r3; ub = u3; cd = f3 > 0.f ? 7u : 3u; }
+        o[j] = (short)ub;
+        packed |= (unsigned long long)cd << (8 * j);
+    }
+    reinterpret_cast<s16x8*>(y)[i] = o;
+    reinterpret_cast<unsigned long long*>(code)[i] = packed;
+}
+
+// backward partials over POOLED rows: only the window's winner carries
+// gradient, so sum(dy_eff) and sum(dy_eff*xhat) need one term per window.
+// Same [2][C][S] slab as k_bn_bwd_partial; k_bn_bwd_combine follows with
+// the FULL-resolution M.
+__global__ void k_bn_bwd_partial_pool2(const bf16* __restrict__ x,
+                                       const bf16* __restrict__ dy,
+                                       const unsigned char* __restrict__ code,
+                                       const float* __restrict__ save_mean,
+                                       const float* __restrict__ save_invstd,
+                                       long Mp, int C, int S, int W,
+                                       FastDiv wo_div,
+                                       float* __restrict__ slab) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* red = reinterpret_cast<float*>(smem);
+    const int cpg = C >> 3;
+    const int c8 = threadIdx.x % cpg;
+    const int walker = threadIdx.x / cpg;
+    const int nw = blockDim.x / cpg;
+    const int s = blockIdx.x;
+    float mean[8], invstd[8];
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        mean[j] = save_mean[c8 * 8 + j];
+        invstd[j] = save_invstd[c8 * 8 + j];
+    }
+    float sum_dy[8] = {}, sum_dyx[8] = {};
+    const int wv = W * cpg;
+    const long rstep = (long)S * nw;
+    for (long pr = (long)s * nw + walker; pr < Mp; pr += rstep) {
+        const s16x8* base = reinterpret_cast<const s16x8*>(
+            x + pool2_origin((unsigned)pr, wo_div) * C) + c8;
+        s16x8 v0 = base[0];
+        s16x8 v1 = base[cpg];
+        s16x8 v2 = base[wv];
+        s16x8 v3 = base[wv + cpg];
+        s16x8 vg = reinterpret_cast<const s16x8*>(dy + pr * C)[c8];
+        unsigned long long cw =
+            reinterpret_cast<const unsigned long long*>(code)[pr * cpg + c8];
+        #pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            unsigned cd = (unsigned)(cw >> (8 * j)) & 7u;
+            unsigned arg = cd & 3u;
+            short xs = arg == 0 ? v0[j] : arg == 1 ? v1[j]
+                     : arg == 2 ? v2[j] : v3[j];
+            float g = (cd & 4u) ? us2f((unsigned short)vg[j]) : 0.f;
+            float xh = (us2f((unsigned short)xs) - mean[j]) * invstd[j];
+            sum_dy[j] += g;
+            sum_dyx[j] = fmaf(g, xh, sum_dyx[j]);
+        }
+    }
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        red[walker * C + c8 * 8 + j] = sum_dy[j];
+        red[nw * C + walker * C + c8 * 8 + j] = sum_dyx[j];
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+        float a = 0.f, b = 0.f;
+        for (int w = 0; w < nw; ++w) {
+            a += red[w * C + c];
+            b += red[nw * C + w * C + c];
+        }
+        slab[(long)c * S + s] = a;
+        slab[(long)C * S + (long)c * S + s] = b;
+    }
+}
+
+// dx over pooled rows: all four window positions are written,
+// dx = a[c] * (dy_eff - b[c] - xhat * c[c]) with dy_eff = dy at the
+// positive winner and 0 elsewhere.  The four window loads are the memory
+// parallelism the 2-deep unroll buys in k_bn_bwd_dx — no deeper staging.
+__global__ void k_bn_bwd_dx_pool2(const bf16* __restrict__ x,
+                                  const bf16* __restrict__ dy,
+                                  const unsigned char* __restrict__ code,
+                                  const float* __restrict__ save_mean,
+                                  const float* __restrict__ save_invstd,
+                                  const float* __restrict__ coef_a,
+                                  const float* __restrict__ coef_b,
+                                  const float* __restrict__ coef_c,
+                                  bf16* __restrict__ dx,
+                                  long Mp, int C, int W, FastDiv wo_div) {
+    const int cpg = C >> 3;
+    const int c8 = threadIdx.x % cpg;
+    const int walker = threadIdx.x / cpg;
+    const int nw = blockDim.x / cpg;
+    float mean[8], invstd[8], ca[8], cb[8], cc[8];
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        int c = c8 * 8 + j;
+        mean[j] = save_mean[c];
+        invstd[j] = save_invstd[c];
+        ca[j] = coef_a[c];
+        cb[j] = coef_b[c];
+        cc[j] = coef_c[c];
+    }
+    const int wv = W * cpg;
+    const long rstride = (long)gridDim.x * nw;
+    for (long pr = (long)blockIdx.x * nw + walker; pr < Mp; pr += rstride) {
+        const long org = pool2_origin((unsigned)pr, wo_div) * C;
+        const s16x8* base = reinterpret_cast<const s16x8*>(x + org) + c8;
+        s16x8 v0 = base[0];
+        s16x8 v1 = base[cpg];
+        s16x8 v2 = base[wv];
+        s16x8 v3 = base[wv + cpg];
+        s16x8 vg = reinterpret_cast<const s16x8*>(dy + pr * C)[c8];
+        unsigned long long cw =
+            reinterpret_cast<const unsigned long long*>(code)[pr * cpg + c8];
+        s16x8 o0, o1, o2, o3;
+        #pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            unsigned cd = (unsigned)(cw >> (8 * j)) & 7u;
+            unsigned sel = (cd & 4u) ? (cd & 3u) : 4u;   // 4: nobody wins
+            float g = us2f((unsigned short)vg[j]);
+            float xh0 = (us2f((unsigned short)v0[j]) - mean[j]) * invstd[j];
+            float xh1 = (us2f((unsigned short)v1[j]) - mean[j]) * invstd[j];
+            float xh2 = (us2f((unsigned short)v2[j]) - mean[j]) * invstd[j];
+            float xh3 = (us2f((unsigned short)v3[j]) - mean[j]) * invstd[j];
+            o0[j] = (short)f2us(ca[j] * ((sel == 0 ? g : 0.f) - cb[j] - xh0 * cc[j]));
+            o1[j] = (short)f2us(ca[j] * ((sel == 1 ? g : 0.f) - cb[j] - xh1 * cc[j]));
+            o2[j] = (short)f2us(ca[j] * ((sel == 2 ? g : 0.f) - cb[j] - xh2 * cc[j]));
+            o3[j] = (short)f2us(ca[j] * ((sel == 3 ? g : 0.f) - cb[j] - xh3 * cc[j]));
+        }
+        s16x8* ob = reinterpret_cast<s16x8*>(dx + org) + c8;
+        ob[0] = o0;
+        ob[cpg] = o1;
+        ob[wv] = o2;
+        ob[wv + cpg] = o3;
+    }
+}
+
 // ----------------------------------------------- single-pass backward ------
 //
 // DDPX_BN1PASS=1: one persistent-grid kernel
@@ -824,5 +1025,155 @@ std::vector<at::Tensor> bn_bwd(at::Tensor x, at::Tensor dy, at::Tensor gamma,
                        fuse_relu, drp);
     HIP_CHECK_LAST();
     if (want_dresid) return {dx, dgamma, dbeta, dresid};
+    return {dx, dgamma, dbeta};
+}
+
+// ---------------------------------------------- BN + ReLU + pool2 hosts ----
+
+static void check_pool2_input(const at::Tensor& x, const char* who) {
+    TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16
+                && x.dim() == 4
+                && x.is_contiguous(at::MemoryFormat::ChannelsLast),
+                who, " needs a channels_last bf16 4-d input");
+    TORCH_CHECK(x.size(1) % 8 == 0, who, " needs C%8==0");
+    TORCH_CHECK(x.size(1) / 8 <= 256, who, " needs C/8<=256");
+    TORCH_CHECK(x.size(2) % 2 == 0 && x.size(3) % 2 == 0,
+                who, " needs even H and W (odd extents stay unfused)");
+    // fd_div is exact below 2^31: pooled 8-channel groups are the largest
+    // index space the kernels divide
+    TORCH_CHECK(x.numel() / 32 < (1l << 31), who, ": input too large");
+}
+
+// BN(train) + ReLU + MaxPool2d(2): returns {y_pooled, save_mean,
+// save_invstd, code}.  Statistics, running-stat update and pre_stats are
+// exactly bn_fwd_train's (k_bn_partial / k_bn_combine over the
+// full-resolution x).
+std::vector<at::Tensor> bn_fwd_train_pool2(at::Tensor x, at::Tensor gamma,
+                                           at::Tensor beta,
+                                           at::Tensor running_mean,
+                                           at::Tensor running_var,
+                                           double momentum, double eps,
+                                           c10::optional<at::Tensor> pre_stats) {
+    check_pool2_input(x, "bn_fwd_train_pool2");
+    long M; int C;
+    shape_mc(x, M, C);
+    const int N = x.size(0), H = x.size(2), W = x.size(3);
+    const int Ho = H / 2, Wo = W / 2;
+    auto stream = at::hip::getCurrentHIPStream();
+    auto fopts = gamma.options().dtype(at::kFloat);
+    int block = pick_block(C);
+    int nw = block / (C / 8);
+    TORCH_CHECK(!pre_stats.has_value()
+                || (pre_stats->dim() == 3 && pre_stats->size(0) == 2
+                    && pre_stats->size(1) == C),
+                "bn_fwd_train_pool2: pre_stats must be [2][C][S]");
+    int S = pre_stats.has_value() ? (int)pre_stats->size(2)
+                                  : bn_splits(M, nw);
+    auto slab = pre_stats.has_value() ? *pre_stats
+                                      : at::empty({2, C, S}, fopts);
+    auto save_mean = at::empty({C}, fopts);
+    auto save_invstd = at::empty({C}, fopts);
+    auto scale = at::empty({C}, fopts);
+    auto shift = at::empty({C}, fopts);
+    auto y = at::empty({N, C, Ho, Wo},
+                       x.options().memory_format(at::MemoryFormat::ChannelsLast));
+    auto code = at::empty({N, Ho, Wo, C}, x.options().dtype(at::kByte));
+    const bf16* xp = reinterpret_cast<const bf16*>(x.data_ptr());
+    int lds = 2 * nw * C * 4;
+
+    if (!pre_stats.has_value()) {
+        hipLaunchKernelGGL(k_bn_partial, dim3(S), dim3(block), lds,
+                           stream.stream(), xp, M, C, S,
+                           slab.data_ptr<float>());
+        HIP_CHECK_LAST();
+    }
+    hipLaunchKernelGGL(k_bn_combine, dim3(ceil_div_i(C, 4)), dim3(256), 0,
+                       stream.stream(), slab.data_ptr<float>(), S, C, M,
+                       gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                       running_mean.data_ptr<float>(),
+                       running_var.data_ptr<float>(),
+                       (float)momentum, (float)eps,
+                       save_mean.data_ptr<float>(),
+                       save_invstd.data_ptr<float>(),
+                       scale.data_ptr<float>(), shift.data_ptr<float>());
+    HIP_CHECK_LAST();
+    long tv = (M / 4) * (C / 8);
+    FastDiv cv_div, wo_div;
+    cv_div.init((unsigned)(C / 8));
+    wo_div.init((unsigned)Wo);
+    hipLaunchKernelGGL(k_bn_apply_pool2_v8, dim3(ceil_div_i(tv, 256)),
+                       dim3(256), 0, stream.stream(), xp,
+                       reinterpret_cast<bf16*>(y.data_ptr()),
+                       code.data_ptr<unsigned char>(),
+                       scale.data_ptr<float>(), shift.data_ptr<float>(),
+                       tv, C / 8, W, cv_div, wo_div);
+    HIP_CHECK_LAST();
+    return {y, save_mean, save_invstd, code};
+}
+
+// Backward of bn_fwd_train_pool2: dy_pooled is the gradient of the POOLED
+// output; returns {dx (full resolution), dgamma, dbeta}.
+std::vector<at::Tensor> bn_bwd_pool2(at::Tensor x, at::Tensor dy_pooled,
+                                     at::Tensor gamma, at::Tensor save_mean,
+                                     at::Tensor save_invstd, at::Tensor code) {
+    check_pool2_input(x, "bn_bwd_pool2");
+    long M; int C;
+    shape_mc(x, M, C);
+    const int N = x.size(0), H = x.size(2), W = x.size(3);
+    const int Ho = H / 2, Wo = W / 2;
+    TORCH_CHECK(dy_pooled.is_cuda()
+                && dy_pooled.scalar_type() == at::kBFloat16
+                && dy_pooled.dim() == 4 && dy_pooled.size(0) == N
+                && dy_pooled.size(1) == C && dy_pooled.size(2) == Ho
+                && dy_pooled.size(3) == Wo
+                && dy_pooled.is_contiguous(at::MemoryFormat::ChannelsLast),
+                "bn_bwd_pool2 needs a channels_last bf16 pooled dy");
+    const long Mp = M / 4;
+    TORCH_CHECK(code.scalar_type() == at::kByte && code.is_contiguous()
+                && code.numel() == Mp * C,
+                "bn_bwd_pool2 needs the code bytes from bn_fwd_train_pool2");
+    auto stream = at::hip::getCurrentHIPStream();
+    auto fopts = gamma.options().dtype(at::kFloat);
+    int block = pick_block(C);
+    int nw = block / (C / 8);
+    int S = bn_splits(Mp, nw);
+    auto slab = at::empty({2, C, S}, fopts);
+    auto dgamma = at::empty({C}, fopts);
+    auto dbeta = at::empty({C}, fopts);
+    auto ca = at::empty({C}, fopts);
+    auto cb = at::empty({C}, fopts);
+    auto cc = at::empty({C}, fopts);
+    auto dx = at::empty_like(
+        x, x.options().memory_format(at::MemoryFormat::ChannelsLast));
+    const bf16* xp = reinterpret_cast<const bf16*>(x.data_ptr());
+    const bf16* dyp = reinterpret_cast<const bf16*>(dy_pooled.data_ptr());
+    const unsigned char* cp = code.data_ptr<unsigned char>();
+    int lds = 2 * nw * C * 4;
+    FastDiv wo_div;
+    wo_div.init((unsigned)Wo);
+
+    hipLaunchKernelGGL(k_bn_bwd_partial_pool2, dim3(S), dim3(block), lds,
+                       stream.stream(), xp, dyp, cp,
+                       save_mean.data_ptr<float>(),
+                       save_invstd.data_ptr<float>(), Mp, C, S, W, wo_div,
+                       slab.data_ptr<float>());
+    HIP_CHECK_LAST();
+    // M, not Mp: coef_b/coef_c are means over the full-resolution rows
+    hipLaunchKernelGGL(k_bn_bwd_combine, dim3(ceil_div_i(C, 4)), dim3(256), 0,
+                       stream.stream(), slab.data_ptr<float>(), S, C, M,
+                       gamma.data_ptr<float>(), save_invstd.data_ptr<float>(),
+                       dgamma.data_ptr<float>(), dbeta.data_ptr<float>(),
+                       ca.data_ptr<float>(), cb.data_ptr<float>(),
+                       cc.data_ptr<float>());
+    HIP_CHECK_LAST();
+    int dxblocks = (int)std::max<long>(1, std::min<long>(2048, Mp / nw));
+    hipLaunchKernelGGL(k_bn_bwd_dx_pool2, dim3(dxblocks), dim3(block), 0,
+                       stream.stream(), xp, dyp, cp,
+                       save_mean.data_ptr<float>(),
+                       save_invstd.data_ptr<float>(), ca.data_ptr<float>(),
+                       cb.data_ptr<float>(), cc.data_ptr<float>(),
+                       reinterpret_cast<bf16*>(dx.data_ptr()), Mp, C, W,
+                       wo_div);
+    HIP_CHECK_LAST();
     return {dx, dgamma, dbeta};
 }

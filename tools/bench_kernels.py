@@ -1,6 +1,7 @@
 """Micro-benchmark of the HIP conv kernels at the workload's shapes.
 
 Usage (on a GPU box):  python tools/bench_kernels.py [--resnet]
+                       python tools/bench_kernels.py --bn | --bnpool
 
 Times conv fwd/dgrad/wgrad per shape with HIP events (200 reps after 20
 warmup) and prints achieved TFLOP/s next to microseconds, so kernel A/B
@@ -114,15 +115,63 @@ def bench_bn(reps):
         print(f"{name:6s} {'bwd':10s} {us:9.1f} {(5.13*nbytes)/us/1e3:8.0f}")
 
 
+BNPOOL_SHAPES = [
+    # Toy_Net's two BN(fuse_relu) -> MaxPool2d(2) junctions at B=1024
+    ("toy2", 1024, 128, 24, 24),
+    ("toy4", 1024, 512, 8, 8),
+]
+
+
+def bench_bnpool(reps):
+    """BN+ReLU -> 2x2 max-pool junction, fwd and bwd: the unfused kernel
+    pair against the fused bn_*_pool2 entry points (statistics pass
+    included on both sides)."""
+    ext = load_extension(required=True)
+    dev = torch.device("cuda:0")
+    print(f"{'shape':6s} {'op':6s} {'unfused us':>11s} {'fused us':>9s}")
+    for name, N, C, H, W in BNPOOL_SHAPES:
+        x = torch.randn(N, C, H, W, device=dev).to(torch.bfloat16).contiguous(memory_format=CL)
+        dyp = torch.randn(N, C, H // 2, W // 2, device=dev).to(torch.bfloat16)\
+            .contiguous(memory_format=CL)
+        g = torch.rand(C, device=dev) + 0.5
+        b = torch.randn(C, device=dev)
+        rm = torch.zeros(C, device=dev)
+        rv = torch.ones(C, device=dev)
+
+        def fwd_unfused():
+            y = ext.bn_fwd_train(x, g, b, rm, rv, 0.1, 1e-5, True, None)[0]
+            return ext.maxpool2x2_fwd(y)
+        us_u = time_op(fwd_unfused, reps)
+        us_f = time_op(lambda: ext.bn_fwd_train_pool2(x, g, b, rm, rv, 0.1,
+                                                      1e-5), reps)
+        print(f"{name:6s} {'fwd':6s} {us_u:11.1f} {us_f:9.1f}")
+
+        y, sm, si, mask = ext.bn_fwd_train(x, g, b, rm, rv, 0.1, 1e-5, True, None)
+        _, idx = ext.maxpool2x2_fwd(y)
+        _, sm2, si2, code = ext.bn_fwd_train_pool2(x, g, b, rm, rv, 0.1, 1e-5)
+
+        def bwd_unfused():
+            dy = ext.maxpool2x2_bwd(dyp, idx, H, W)
+            return ext.bn_bwd(x, dy, g, sm, si, mask, True, False)
+        us_u = time_op(bwd_unfused, reps)
+        us_f = time_op(lambda: ext.bn_bwd_pool2(x, dyp, g, sm2, si2, code),
+                       reps)
+        print(f"{name:6s} {'bwd':6s} {us_u:11.1f} {us_f:9.1f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--resnet", action="store_true")
     ap.add_argument("--functional", action="store_true")
     ap.add_argument("--bn", action="store_true")
+    ap.add_argument("--bnpool", action="store_true")
     ap.add_argument("--reps", type=int, default=200)
     args = ap.parse_args()
     if args.bn:
         bench_bn(args.reps)
+        return
+    if args.bnpool:
+        bench_bnpool(args.reps)
         return
     if args.functional:
         load_extension(required=True)
