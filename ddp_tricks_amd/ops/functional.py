@@ -189,7 +189,11 @@ def _conv_bwd_impl(ctx, dy):
     K, C, R, S = w_shape
     dx = dw = db = None
     if ctx.needs_input_grad[0]:
-        wt2 = weight_variant(weight, "wt2_p8" if pad8 else "wt2")
+        # the dgrad kernel writes 8-channel chunks: a C<8 conv whose
+        # UNPADDED x was saved (small spatial) still takes the padded
+        # operand, and the pad channels are sliced off below
+        p8 = pad8 or C < 8
+        wt2 = weight_variant(weight, "wt2_p8" if p8 else "wt2")
         box = getattr(ctx, "bn_box", None)
         # stashed junction skip-grad (only ever set for stride-1 non-pad8
         # convs — see _attach_skipbox call sites)
@@ -203,10 +207,11 @@ def _conv_bwd_impl(ctx, dy):
             box["slab"] = slab
             box["dx_ref"] = dx
         else:
-            dx = ext.conv2d_dgrad(dyb, wt2, xb.shape[0], xb.shape[1],
+            dx = ext.conv2d_dgrad(dyb, wt2, xb.shape[0],
+                                  8 if p8 else xb.shape[1],
                                   xb.shape[2], xb.shape[3], R, S,
                                   stride, padding, g)
-            if pad8:
+            if p8:
                 dx = dx[:, :C]
             if x_dtype == torch.float32:
                 dx = dx.float()
@@ -279,10 +284,21 @@ class _HIPConv2d(torch.autograd.Function):
         return dx, dw, db, None, None
 
 
+def _uniform(v, name):
+    """The HIP conv kernels take ONE stride and ONE padding for both
+    spatial dims: reduce a uniform tuple to its value, refuse any other."""
+    if isinstance(v, (tuple, list)):
+        if any(e != v[0] for e in v):
+            raise ValueError(
+                f"HIP conv2d needs a uniform {name}, got {tuple(v)}")
+        return v[0]
+    return v
+
+
 def conv2d(x, weight, bias=None, stride=1, padding=0):
-    stride = stride[0] if isinstance(stride, (tuple, list)) else stride
-    padding = padding[0] if isinstance(padding, (tuple, list)) else padding
     if x.is_cuda and require_ext_for(x) is not None:
+        stride = _uniform(stride, "stride")
+        padding = _uniform(padding, "padding")
         # NOTE: a 1x1-as-GEMM route through the linear kernels was tried and
         # REVERTED — measured 2.6 ms vs 0.27 ms for the conv path at
         # ResNet-50's [M~800k, 64x64] shapes (the GEMM ladder's split-K is
@@ -711,10 +727,8 @@ def conv_bn(conv_mod, bn_mod, x, residual=None, pool=None):
                                                  (1, 1)) in ((1, 1), 1))
     stats = None
     if use_stats:
-        stride = conv_mod.stride[0] if isinstance(conv_mod.stride, tuple) \
-            else conv_mod.stride
-        padding = conv_mod.padding[0] if isinstance(conv_mod.padding, tuple) \
-            else conv_mod.padding
+        stride = _uniform(conv_mod.stride, "stride")
+        padding = _uniform(conv_mod.padding, "padding")
         y, stats = _HIPConv2dStats.apply(x, conv_mod.weight, conv_mod.bias,
                                          stride, padding)
     else:

@@ -368,8 +368,10 @@ void conv_gemm_body(const bf16* __restrict__ Asrc,
                 }
                 *reinterpret_cast<bf16x8_t*>(&out[row * Nout + col]) = v;
                 if (do_bn) {
+                    // mask byte of GLOBAL channel group col/8 (col = n0 +
+                    // csub: blockIdx.y > 0 tiles must not reuse group 0's)
                     unsigned m8 = bn.mask
-                        ? bn.mask[row * (Nout >> 3) + (csub >> 3)] : 0xffu;
+                        ? bn.mask[row * (Nout >> 3) + (col >> 3)] : 0xffu;
                     s16x8 xv = *reinterpret_cast<const s16x8*>(
                         &bn.x[row * Nout + col]);
                     #pragma unroll
@@ -1485,7 +1487,9 @@ __global__ void k_wgrad_small_rsc_combine(const float* __restrict__ slab,
     dw[((long)ko * cs.C + c) * (cs.R * cs.S) + rs] = v;
 }
 
-// conv1-style wgrad (Cin < 8): per-(rs, split) block, lanes along Ko
+// conv1-style wgrad (Cin < 8): per-(rs, split, ko-block) block, lanes along
+// Ko — blockIdx.z walks Ko in 64-wide blocks so every output channel is
+// covered (the combine reads all Ko columns of the slab)
 __global__ void k_wgrad_small_cin(const bf16* __restrict__ dy,
                                   const bf16* __restrict__ x,
                                   float* __restrict__ slab, ConvShape cs,
@@ -1494,7 +1498,8 @@ __global__ void k_wgrad_small_cin(const bf16* __restrict__ dy,
     int split = blockIdx.y;
     int c = rsc % cs.C, rsq = rsc / cs.C;
     int r = rsq / cs.S, s = rsq % cs.S;
-    int ko = threadIdx.x & 63;
+    int kl = threadIdx.x & 63;
+    int ko = blockIdx.z * 64 + kl;
     int walker = threadIdx.x >> 6;    // 4 walkers
     __shared__ float red[4][64];
     float acc = 0.f;
@@ -1509,12 +1514,12 @@ __global__ void k_wgrad_small_cin(const bf16* __restrict__ dy,
             acc = fmaf(bf2f(dy[gm * cs.Ko + ko]), xv, acc);
         }
     }
-    red[walker][ko] = acc;
+    red[walker][kl] = acc;
     __syncthreads();
     if (walker == 0 && ko < cs.Ko) {
         float t = 0.f;
         #pragma unroll
-        for (int w = 0; w < 4; ++w) t += red[w][ko];
+        for (int w = 0; w < 4; ++w) t += red[w][kl];
         // slab layout [S][rsc_total][Ko]
         slab[((long)split * gridDim.x + rsc) * cs.Ko + ko] = t;
     }
@@ -1577,6 +1582,8 @@ at::Tensor conv2d_fwd(at::Tensor x, at::Tensor w,
                            stream.stream(), xp, wp, bp, yp, cs, M);
     } else {
         TORCH_CHECK(cs.C % 8 == 0, "conv fwd needs C % 8 == 0");
+        // the staged epilogue stores 16 B (8-channel) chunks per row
+        TORCH_CHECK(cs.Ko % 8 == 0, "conv fwd needs Ko % 8 == 0");
         static const char* tbn_env = getenv("DDPX_CONV_TBN64");
         if (cs.Ko >= 128 && !tbn_env) {
             dim3 grid(ceil_div_i(M, CBM), ceil_div_i(cs.Ko, 128));
@@ -1609,7 +1616,9 @@ at::Tensor conv2d_dgrad(at::Tensor dy, at::Tensor wt2, long N, long C,
     cs.Ko = dy.size(1); cs.P = dy.size(2); cs.Q = dy.size(3);
     cs.R = R; cs.S = S; cs.stride = stride; cs.pad = pad;
     init_fastdiv(cs);
-    TORCH_CHECK(cs.Ko % 8 == 0);
+    TORCH_CHECK(cs.Ko % 8 == 0, "conv dgrad needs Ko % 8 == 0");
+    // the staged epilogue stores 16 B (8-channel) chunks per dx row
+    TORCH_CHECK(cs.C % 8 == 0, "conv dgrad needs C % 8 == 0");
     int Kgemm = cs.R * cs.S * cs.Ko;
     long M = (long)cs.N * cs.H * cs.W;
     auto dx = at::empty({(long)cs.N, (long)cs.C, (long)cs.H, (long)cs.W},
@@ -1837,8 +1846,9 @@ at::Tensor conv2d_wgrad(at::Tensor dy, at::Tensor x, long R, long S,
         int S_ = 64;
         auto slab = at::empty({S_, rsc_total, cs.Ko},
                               x.options().dtype(at::kFloat));
-        hipLaunchKernelGGL(k_wgrad_small_cin, dim3(rsc_total, S_), dim3(256),
-                           0, stream.stream(), dyp, xp,
+        hipLaunchKernelGGL(k_wgrad_small_cin,
+                           dim3(rsc_total, S_, ceil_div_i(cs.Ko, 64)),
+                           dim3(256), 0, stream.stream(), dyp, xp,
                            slab.data_ptr<float>(), cs, M, S_);
         HIP_CHECK_LAST();
         int total = rsc_total * cs.Ko;
@@ -1962,6 +1972,7 @@ std::vector<at::Tensor> conv2d_fwd_stats(at::Tensor x, at::Tensor w,
     ConvShape cs = make_shape(x, w.size(0), w.size(2), w.size(3),
                               (int)stride, (int)pad);
     TORCH_CHECK(cs.C % 8 == 0, "stats path needs the MFMA conv (C%8==0)");
+    TORCH_CHECK(cs.Ko % 8 == 0, "conv fwd needs Ko % 8 == 0");
     int Kgemm = cs.R * cs.S * cs.C;
     long M = (long)cs.N * cs.P * cs.Q;
     auto y = at::empty({cs.N, cs.Ko, cs.P, cs.Q},
