@@ -17,7 +17,12 @@ that exact API shape with MI355X-native mechanics:
     gradient buckets, folding in the 1/world_size gradient average
     (all-reduce is SUM) — one kernel pass over the 23 MB gradient payload
     (SURVEY N4 disposition);
-  * on overflow the wrapped optimizer's next step is skipped, like apex.
+  * on overflow the wrapped optimizer's next step is skipped, like apex;
+  * optional global gradient-norm clipping (``max_grad_norm``): the sum of
+    squares rides on the unscale pass, a one-block finalize leaves the
+    norm and the clip coefficient on device, and the next ``fused_sgd``
+    applies the coefficient while it reads the gradients (lazy clip) —
+    no extra pass over gradient memory and no host sync.
 """
 from __future__ import annotations
 
@@ -67,6 +72,13 @@ class _AmpState:
         #                              exact backoff/growth sequencing
         self.async_steps = 0         # backward count since last scaler sync
         self.async_mode = False
+        # global gradient-norm clipping (off unless max_grad_norm > 0)
+        self.max_grad_norm = 0.0
+        self.norm_partials = None    # per-chunk sums of squares (GPU)
+        self.norm_out = None         # {pre-clip norm, clip coefficient}
+        self.norm_stats = None       # {sum, max, #clipped, #finite steps}
+        self.last_norm = None        # 0-dim tensor: norm of the last backward
+        self.lazy_clip = False       # coefficient pending for fused_sgd
 
 
 _state = _AmpState()
@@ -87,6 +99,74 @@ def _device_buffers(device):
 def pending_found_inf():
     """Device-side overflow flag for the fused optimizer kernels (or None)."""
     return _state.found_inf if _state.async_mode else None
+
+
+def _clip_buffers(device, nchunks: int = 0):
+    """Norm/coefficient/telemetry buffers, allocated once per device (the
+    partials grow only if a longer gradient list shows up)."""
+    if _state.norm_out is None or _state.norm_out.device != device:
+        _state.norm_out = torch.zeros(2, dtype=torch.float32, device=device)
+        _state.norm_stats = torch.zeros(4, dtype=torch.float32, device=device)
+        _state.norm_partials = None
+    if nchunks and (_state.norm_partials is None
+                    or _state.norm_partials.numel() < nchunks):
+        _state.norm_partials = torch.zeros(nchunks, dtype=torch.float32,
+                                           device=device)
+    return _state.norm_partials, _state.norm_out, _state.norm_stats
+
+
+def _clip_fused(optimizer) -> bool:
+    """Lazy clip only when the step that follows is the fused SGD (possibly
+    under Lookahead) — it is the one consumer of the pending coefficient;
+    any other optimizer gets its gradients clipped in place."""
+    if os.environ.get("DDPX_CLIP_FUSED", "1") == "0":
+        return False
+    from ..ops.optim import FusedSGD
+    inner = optimizer
+    while inner is not None and not isinstance(inner, FusedSGD):
+        inner = getattr(inner, "optimizer", None)
+    return inner is not None
+
+
+def pending_grad_scale():
+    """Device-side clip coefficient for the next fused_sgd when the lazy
+    clip is armed (gradients were left unclipped by scale_loss), else None."""
+    return _state.norm_out[1:2] if _state.lazy_clip else None
+
+
+def last_grad_norm():
+    """Pre-clip global gradient 2-norm of the last backward — a 0-dim tensor
+    on the gradients' device (None before the first clipped backward)."""
+    return _state.last_norm
+
+
+def pop_grad_norm_stats() -> dict:
+    """Gradient-norm telemetry since the last pop: mean and max of the
+    pre-clip norm, fraction of steps clipped, number of (finite) steps.  One
+    host sync; resets the window.  Call once per epoch."""
+    if _state.norm_stats is None:
+        return {"mean": 0.0, "max": 0.0, "clipped_frac": 0.0, "steps": 0}
+    total, mx, clipped, steps = _state.norm_stats.tolist()
+    _state.norm_stats.zero_()
+    return {"mean": total / steps if steps else 0.0, "max": mx,
+            "clipped_frac": clipped / steps if steps else 0.0,
+            "steps": int(steps)}
+
+
+def _clip_in_place(tensors, measure_only: bool = False) -> None:
+    """Sync/CPU/amp-off clip: norm + in-place scale through
+    ops.functional (HIP kernels on GPU, the torch formula on CPU)."""
+    if not tensors:
+        return
+    from ..ops.functional import clip_grad_norm_impl
+    _, out, stats = _clip_buffers(tensors[0].device)
+    if measure_only:
+        # overflow: report the (non-finite) norm, touch nothing else
+        clip_grad_norm_impl(tensors, 0.0, out=out)
+    else:
+        clip_grad_norm_impl(tensors, _state.max_grad_norm, stats=stats,
+                            out=out)
+    _state.last_norm = out[0]
 
 
 def maybe_sync_scaler() -> None:
@@ -152,11 +232,22 @@ def register_ddp(ddp_model) -> None:
     _state.ddp_model = ddp_model
 
 
-def initialize(model, optimizers, opt_level: str = "O1", loss_scale="dynamic"):
-    """apex-compatible entry point (model, optimizer [, ...]) -> same tuple."""
+def initialize(model, optimizers, opt_level: str = "O1", loss_scale="dynamic",
+               max_grad_norm: Optional[float] = None):
+    """apex-compatible entry point (model, optimizer [, ...]) -> same tuple.
+
+    ``max_grad_norm`` (extension): clip the global gradient 2-norm inside
+    ``scale_loss``; None or 0 = off."""
     if opt_level not in ("O0", "O1", "O2"):
         raise ValueError(f"unsupported opt_level {opt_level!r}")
     _state.enabled = opt_level != "O0"
+    _state.max_grad_norm = float(max_grad_norm or 0.0)
+    if _state.max_grad_norm < 0:
+        raise ValueError(f"max_grad_norm must be >= 0, got {max_grad_norm}")
+    _state.lazy_clip = False
+    _state.last_norm = None
+    if _state.norm_stats is not None:
+        _state.norm_stats.zero_()
     if loss_scale == "dynamic" or loss_scale is None:
         _state.scaler = DynamicLossScaler()
     else:
@@ -219,8 +310,13 @@ def scale_loss(loss, optimizer, delay_unscale: bool = False):
     """
     if not _state.enabled or _state.scaler is None:
         yield loss
+        tensors = None
         if _state.ddp_model is not None:
             _state.ddp_model.finalize_backward(average=True)
+            tensors = _state.ddp_model.bucket_flats()
+        if _state.max_grad_norm > 0:
+            _state.lazy_clip = False
+            _clip_in_place(tensors or _collect_grads(optimizer))
         return
 
     scaler = _state.scaler
@@ -235,6 +331,8 @@ def scale_loss(loss, optimizer, delay_unscale: bool = False):
     if tensors is None:
         tensors = _collect_grads(optimizer)
     inv = 1.0 / (scaler.scale * world)
+    clip = _state.max_grad_norm > 0
+    _state.lazy_clip = False
 
     # Async path (GPU + HIP ext): unscale+check leaves the flag on device;
     # the fused SGD/Lookahead kernels skip themselves when it is set and
@@ -248,7 +346,23 @@ def scale_loss(loss, optimizer, delay_unscale: bool = False):
             _state.async_steps += 1
             fi = _device_buffers(tensors[0].device)
             fi.zero_()  # stream-ordered: prior step's kernels already read it
-            ext.multi_tensor_unscale(tensors, fi, inv)
+            if clip:
+                # sum of squares rides on the unscale pass; the coefficient
+                # stays on device for the next fused_sgd (lazy clip) unless
+                # DDPX_CLIP_FUSED=0 asks for the in-place scale pass
+                from ..ops.functional import clip_grad_norm_impl, num_chunks
+                partials, out, stats = _clip_buffers(
+                    tensors[0].device, max(1, num_chunks(tensors, ext)))
+                ext.multi_tensor_unscale(tensors, fi, inv, partials)
+                lazy = _clip_fused(optimizer)
+                clip_grad_norm_impl(tensors, _state.max_grad_norm,
+                                    found_inf=fi, stats=stats, out=out,
+                                    partials=partials, presummed=True,
+                                    scale=not lazy)
+                _state.last_norm = out[0]
+                _state.lazy_clip = lazy
+            else:
+                ext.multi_tensor_unscale(tensors, fi, inv)
             _state.overflow_count += fi
             # device-side (no host sync) record of first/last overflow step
             of = fi > 0
@@ -265,6 +379,8 @@ def scale_loss(loss, optimizer, delay_unscale: bool = False):
     found_inf = _unscale_and_check(tensors, inv)
     scaler.update(found_inf)
     _state.last_overflow = found_inf
+    if clip:
+        _clip_in_place(tensors, measure_only=found_inf)
 
 
 def master_params(optimizer):

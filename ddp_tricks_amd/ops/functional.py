@@ -712,6 +712,97 @@ def argmax_correct(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     return (torch.argmax(logits, dim=1) == target).sum()
 
 
+def _grad_list(tensors_or_params):
+    if torch.is_tensor(tensors_or_params):
+        tensors_or_params = [tensors_or_params]
+    out = []
+    for t in tensors_or_params:
+        if isinstance(t, torch.nn.Parameter):
+            t = t.grad
+        if t is not None:
+            out.append(t)
+    return out
+
+
+def num_chunks(tensors, ext) -> int:
+    """Partials needed by the multi-tensor square-sum kernels: one per
+    (tensor, MT_CHUNK-element chunk)."""
+    ch = ext.MT_CHUNK
+    return sum((t.numel() + ch - 1) // ch for t in tensors)
+
+
+def clip_grad_norm_impl(tensors, max_norm: float, found_inf=None, stats=None,
+                        out=None, partials=None, presummed: bool = False,
+                        scale: bool = True):
+    """Global 2-norm clip over ``tensors`` (gradients themselves), in place.
+
+    out[0] = norm, out[1] = clip coefficient =
+    ``min(1, max_norm / (norm + 1e-6))`` (torch's clip_grad_norm_ formula) —
+    1.0 when ``max_norm <= 0``, the norm is non-finite or ``found_inf`` is
+    set.  ``stats`` is the 4-float telemetry buffer {sum of finite norms,
+    max finite norm, #clipped steps, #finite steps}.  No host sync.
+    Returns ``out`` (2 floats on the tensors' device).
+
+    GPU: square-sum -> finalize -> in-place scale HIP kernels
+    (``presummed``: ``partials`` already hold the chunk sums, from the fused
+    unscale; ``scale=False`` leaves the tensors alone — the lazy clip).
+    CPU: the same formula with torch ops, the sum of squares accumulated in
+    float64 — the oracle for the GPU kernels."""
+    max_norm = float(max_norm or 0.0)
+    dev = tensors[0].device if tensors else (
+        out.device if out is not None else torch.device("cpu"))
+    if out is None:
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+    ext = require_ext_for(tensors[0]) if tensors and tensors[0].is_cuda \
+        else None
+    if ext is not None:
+        n = num_chunks(tensors, ext)
+        if partials is None:
+            partials = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
+        if not presummed:
+            ext.multi_tensor_sqsum(tensors, partials)
+        ext.norm_finalize(partials, n, max_norm, found_inf, out, stats)
+        if scale and max_norm > 0:
+            ext.multi_tensor_scale(tensors, out[1:2], found_inf)
+        return out
+    sq = torch.zeros((), dtype=torch.float64, device=dev)
+    for t in tensors:
+        sq = sq + t.detach().double().pow(2).sum()
+    norm = sq.sqrt().float()
+    ok = torch.isfinite(norm)
+    if found_inf is not None:
+        ok = ok & (found_inf.reshape(()) == 0)
+    one = torch.ones((), dtype=torch.float32, device=dev)
+    coef = one
+    if max_norm > 0:
+        coef = torch.where(ok, (max_norm / (norm + 1e-6)).clamp(max=1.0), one)
+    out[0] = norm
+    out[1] = coef
+    if stats is not None:
+        okf = ok.float()
+        # where(), not multiply: a non-finite norm must leave stats untouched
+        stats[0] += torch.where(ok, norm, torch.zeros_like(norm))
+        stats[1] = torch.where(ok, torch.maximum(stats[1], norm), stats[1])
+        stats[2] += okf * (coef < 1).float()
+        stats[3] += okf
+    if scale and max_norm > 0:
+        with torch.no_grad():
+            for t in tensors:
+                t.mul_(coef)
+    return out
+
+
+def clip_grad_norm_(tensors_or_params, max_norm: float) -> torch.Tensor:
+    """Clip the global gradient 2-norm to ``max_norm`` in place; returns the
+    pre-clip norm as a 0-dim tensor on the gradients' device (no host sync).
+
+    Accepts gradient tensors, or Parameters (their ``.grad`` is clipped).
+    ``max_norm <= 0`` only measures.  Same formula as
+    ``torch.nn.utils.clip_grad_norm_`` (2-norm only); on GPU it runs three
+    multi-tensor HIP launches instead of ATen foreach passes."""
+    return clip_grad_norm_impl(_grad_list(tensors_or_params), max_norm)[0]
+
+
 def conv_bn(conv_mod, bn_mod, x, residual=None, pool=None):
     """Fused producer/consumer: on the GPU training path the conv epilogue
     emits the BN's per-channel partial statistics, and the BN forward skips

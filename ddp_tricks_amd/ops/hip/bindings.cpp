@@ -3,10 +3,19 @@
 
 // elementwise.hip
 void multi_tensor_unscale(std::vector<at::Tensor> grads, at::Tensor found_inf,
-                          double inv_scale);
+                          double inv_scale,
+                          c10::optional<at::Tensor> partials);
+void multi_tensor_sqsum(std::vector<at::Tensor> tensors, at::Tensor partials);
+void norm_finalize(at::Tensor partials, long n, double max_norm,
+                   c10::optional<at::Tensor> found_inf, at::Tensor out,
+                   c10::optional<at::Tensor> stats);
+void multi_tensor_scale(std::vector<at::Tensor> tensors, at::Tensor coef,
+                        c10::optional<at::Tensor> found_inf);
+long mt_chunk_elems();
 void fused_sgd(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
                std::vector<at::Tensor> bufs, double lr, double momentum,
-               double wd, double nesterov, c10::optional<at::Tensor> found_inf);
+               double wd, double nesterov, c10::optional<at::Tensor> found_inf,
+               c10::optional<at::Tensor> grad_scale);
 void fused_lookahead(std::vector<at::Tensor> fast, std::vector<at::Tensor> slow,
                      double alpha, c10::optional<at::Tensor> found_inf);
 at::Tensor cast_to_bf16(at::Tensor x);
@@ -97,11 +106,27 @@ void register_comm(py::module_& m);
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     register_comm(m);
     m.def("multi_tensor_unscale", &multi_tensor_unscale,
-          "fused unscale + inf check over grad tensors");
+          "fused unscale + inf check over grad tensors; with partials also "
+          "the per-chunk sums of squares of the unscaled values",
+          py::arg("grads"), py::arg("found_inf"), py::arg("inv_scale"),
+          py::arg("partials") = c10::nullopt);
+    m.def("multi_tensor_sqsum", &multi_tensor_sqsum,
+          "per-chunk sums of squares (read-only)",
+          py::arg("tensors"), py::arg("partials"));
+    m.def("norm_finalize", &norm_finalize,
+          "partials -> out = {2-norm, clip coefficient} (+ telemetry)",
+          py::arg("partials"), py::arg("n"), py::arg("max_norm"),
+          py::arg("found_inf"), py::arg("out"), py::arg("stats"));
+    m.def("multi_tensor_scale", &multi_tensor_scale,
+          "tensors *= coef[0] in place (device coefficient)",
+          py::arg("tensors"), py::arg("coef"),
+          py::arg("found_inf") = c10::nullopt);
+    m.attr("MT_CHUNK") = mt_chunk_elems();
     m.def("fused_sgd", &fused_sgd, "fused nesterov-momentum SGD step",
           py::arg("params"), py::arg("grads"), py::arg("bufs"), py::arg("lr"),
           py::arg("momentum"), py::arg("wd"), py::arg("nesterov"),
-          py::arg("found_inf") = c10::nullopt);
+          py::arg("found_inf") = c10::nullopt,
+          py::arg("grad_scale") = c10::nullopt);
     m.def("fused_lookahead", &fused_lookahead, "fused Lookahead interpolation",
           py::arg("fast"), py::arg("slow"), py::arg("alpha"),
           py::arg("found_inf") = c10::nullopt);

@@ -3,7 +3,10 @@
 // Implements the implicit native surface of apex amp_C + the fused SGD step
 // (SURVEY N4/N12/N13): multi-tensor unscale+inf-check over the DDP bucket
 // flats, fused SGD(momentum, nesterov) [+ Lookahead interpolation] over the
-// whole parameter list in one launch, bf16<->fp32 casts.
+// whole parameter list in one launch, bf16<->fp32 casts.  Global grad-norm
+// clipping rides on the same two passes: per-chunk sums of squares out of
+// the unscale kernel, a one-block finalize (norm + clip coefficient, on
+// device), and the coefficient applied inside the SGD's gradient read.
 //
 // Multi-tensor scheme: host packs up to MT_MAX tensor pointers + a prefix
 // of chunk offsets into the kernarg struct; blocks map to (tensor, chunk)
@@ -47,32 +50,112 @@ DEV_INLINE void chunk_range(const MTMeta& m, int& t, long& base, long& end) {
 
 // ---------------------------------------------------------------- unscale ---
 
-__global__ void k_mt_unscale(MTMeta m, float inv_scale, float* found_inf) {
-    int t; long base, end;
-    chunk_range(m, t, base, end);
-    float* g = m.b[t];
+// Fixed-order block sum (MT_BLOCK threads): 64-lane wave shuffles, then an
+// LDS tree over the per-wave partials.  No atomics — same inputs, same bits
+// (the bn.hip split-reduction contract).  Result valid in thread 0.
+DEV_INLINE float mt_block_sum(float v) {
+    __shared__ float red[MT_BLOCK / WAVE];
+    v = wave_reduce_sum(v);
+    if ((threadIdx.x & (WAVE - 1)) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    #pragma unroll
+    for (int s = MT_BLOCK / WAVE / 2; s > 0; s >>= 1) {
+        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// One (tensor, chunk) pass shared by the unscale and square-sum kernels.
+// SCALE: g *= inv_scale in place + non-finite check (the amp unscale).
+// NORM:  per-thread fp32 sum of squares of the values written (SCALE) or
+//        read (!SCALE); the element->thread mapping and the accumulation
+//        order are the same either way, so the fused and the read-only
+//        kernels give bitwise-identical partials on identical contents.
+template <bool SCALE, bool NORM>
+DEV_INLINE void mt_chunk_pass(float* g, long base, long end, float inv_scale,
+                              bool& bad, float& acc) {
     long vb = base >> 2, ve = end >> 2;
-    bool bad = false;
     for (long i = vb + threadIdx.x; i < ve; i += MT_BLOCK) {
         f32x4 v = reinterpret_cast<f32x4*>(g)[i];
         #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            v[j] *= inv_scale;
-            if (!isfinite(v[j])) bad = true;
+            if (SCALE) {
+                v[j] *= inv_scale;
+                if (!isfinite(v[j])) bad = true;
+            }
+            if (NORM) acc = fmaf(v[j], v[j], acc);
         }
-        reinterpret_cast<f32x4*>(g)[i] = v;
+        if (SCALE) reinterpret_cast<f32x4*>(g)[i] = v;
     }
     for (long i = ve * 4 + threadIdx.x; i < end; i += MT_BLOCK) {
-        float v = g[i] * inv_scale;
-        if (!isfinite(v)) bad = true;
-        g[i] = v;
+        float v = g[i];
+        if (SCALE) {
+            v *= inv_scale;
+            if (!isfinite(v)) bad = true;
+            g[i] = v;
+        }
+        if (NORM) acc = fmaf(v, v, acc);
     }
-    if (bad) *found_inf = 1.0f;  // racy same-value store: any writer sets it
 }
 
+// NORM=false is the plain amp unscale.  NORM=true also writes the chunk's
+// sum of squares (of the unscaled values) to partials[chunk_base+blockIdx.x];
+// chunk_base = chunks of earlier MT_MAX launch groups, so the partial index
+// is global over the whole tensor list.
+template <bool NORM>
+__global__ void k_mt_unscale(MTMeta m, float inv_scale, float* found_inf,
+                             float* __restrict__ partials, int chunk_base) {
+    int t; long base, end;
+    chunk_range(m, t, base, end);
+    bool bad = false;
+    float acc = 0.f;
+    mt_chunk_pass<true, NORM>(m.b[t], base, end, inv_scale, bad, acc);
+    if (bad) *found_inf = 1.0f;  // racy same-value store: any writer sets it
+    if (NORM) {
+        float s = mt_block_sum(acc);
+        if (threadIdx.x == 0) partials[chunk_base + blockIdx.x] = s;
+    }
+}
+
+// Read-only square-sum with the same partial layout (non-amp path and the
+// standalone clip_grad_norm_).
+__global__ void k_mt_sqsum(MTMeta m, float* __restrict__ partials,
+                           int chunk_base) {
+    int t; long base, end;
+    chunk_range(m, t, base, end);
+    bool bad = false;
+    float acc = 0.f;
+    mt_chunk_pass<false, true>(m.b[t], base, end, 1.0f, bad, acc);
+    float s = mt_block_sum(acc);
+    if (threadIdx.x == 0) partials[chunk_base + blockIdx.x] = s;
+}
+
+static int mt_total_chunks(const std::vector<at::Tensor>& ts) {
+    long total = 0;
+    for (auto& t : ts) total += ceil_div_i(t.numel(), MT_CHUNK);
+    TORCH_CHECK(total < (1L << 31), "multi-tensor list too large");
+    return (int)total;
+}
+
+static float* mt_check_partials(const at::Tensor& partials, int total) {
+    TORCH_CHECK(partials.is_cuda() && partials.scalar_type() == at::kFloat &&
+                partials.is_contiguous(), "partials: contiguous cuda fp32");
+    TORCH_CHECK(partials.numel() >= total, "partials holds ",
+                partials.numel(), " floats, need ", total, " (one per chunk)");
+    return partials.data_ptr<float>();
+}
+
+long mt_chunk_elems() { return MT_CHUNK; }
+
 void multi_tensor_unscale(std::vector<at::Tensor> grads, at::Tensor found_inf,
-                          double inv_scale) {
+                          double inv_scale,
+                          c10::optional<at::Tensor> partials) {
     auto stream = at::hip::getCurrentHIPStream();
+    float* pp = nullptr;
+    if (partials.has_value())
+        pp = mt_check_partials(*partials, mt_total_chunks(grads));
+    int chunk_base = 0;
     for (size_t start = 0; start < grads.size(); start += MT_MAX) {
         MTMeta m{};
         int chunks = 0;
@@ -90,9 +173,158 @@ void multi_tensor_unscale(std::vector<at::Tensor> grads, at::Tensor found_inf,
         m.chunk_start[nt] = chunks;
         m.ntensors = nt;
         if (chunks == 0) continue;
-        hipLaunchKernelGGL(k_mt_unscale, dim3(chunks), dim3(MT_BLOCK), 0,
-                           stream.stream(), m, (float)inv_scale,
-                           found_inf.data_ptr<float>());
+        if (pp)
+            hipLaunchKernelGGL(k_mt_unscale<true>, dim3(chunks),
+                               dim3(MT_BLOCK), 0, stream.stream(), m,
+                               (float)inv_scale, found_inf.data_ptr<float>(),
+                               pp, chunk_base);
+        else
+            hipLaunchKernelGGL(k_mt_unscale<false>, dim3(chunks),
+                               dim3(MT_BLOCK), 0, stream.stream(), m,
+                               (float)inv_scale, found_inf.data_ptr<float>(),
+                               (float*)nullptr, 0);
+        HIP_CHECK_LAST();
+        chunk_base += chunks;
+    }
+}
+
+void multi_tensor_sqsum(std::vector<at::Tensor> tensors, at::Tensor partials) {
+    auto stream = at::hip::getCurrentHIPStream();
+    float* pp = mt_check_partials(partials, mt_total_chunks(tensors));
+    int chunk_base = 0;
+    for (size_t start = 0; start < tensors.size(); start += MT_MAX) {
+        MTMeta m{};
+        int chunks = 0, nt = 0;
+        for (size_t i = start; i < std::min(tensors.size(), start + MT_MAX); ++i) {
+            auto& g = tensors[i];
+            TORCH_CHECK(g.is_cuda() && g.scalar_type() == at::kFloat &&
+                        g.is_contiguous(), "sqsum expects contiguous fp32");
+            m.b[nt] = g.data_ptr<float>();
+            m.sizes[nt] = g.numel();
+            m.chunk_start[nt] = chunks;
+            chunks += ceil_div_i(g.numel(), MT_CHUNK);
+            ++nt;
+        }
+        m.chunk_start[nt] = chunks;
+        m.ntensors = nt;
+        if (chunks == 0) continue;
+        hipLaunchKernelGGL(k_mt_sqsum, dim3(chunks), dim3(MT_BLOCK), 0,
+                           stream.stream(), m, pp, chunk_base);
+        HIP_CHECK_LAST();
+        chunk_base += chunks;
+    }
+}
+
+// ---------------------------------------------------- norm finalize / clip ---
+
+// One block: norm = sqrt(sum of the n chunk partials), summed in double in a
+// fixed order (thread i takes partials i, i+256, ...; then a fixed LDS tree).
+//   out[0] = norm
+//   out[1] = clip coefficient = min(1, max_norm / (norm + 1e-6)), torch's
+//            clip_grad_norm_ formula; 1.0 when clipping is off, the norm is
+//            non-finite or found_inf is set (that step is skipped device-side
+//            anyway, and the coefficient must never be NaN).
+//   stats (optional) = {sum of finite norms, max finite norm,
+//                       #steps with coef < 1, #finite steps}.
+__global__ void k_mt_norm_finalize(const float* __restrict__ partials, int n,
+                                   float max_norm,
+                                   const float* __restrict__ found_inf,
+                                   float* __restrict__ out,
+                                   float* __restrict__ stats) {
+    __shared__ double red[MT_BLOCK];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += MT_BLOCK) s += (double)partials[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    #pragma unroll
+    for (int w = MT_BLOCK / 2; w > 0; w >>= 1) {
+        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    float norm = (float)sqrt(red[0]);
+    bool ok = isfinite(norm) && !(found_inf && *found_inf != 0.0f);
+    float coef = 1.0f;
+    if (ok && max_norm > 0.0f)
+        coef = fminf(1.0f, __fdiv_rn(max_norm, __fadd_rn(norm, 1e-6f)));
+    out[0] = norm;
+    out[1] = coef;
+    if (stats && ok) {
+        stats[0] += norm;
+        stats[1] = fmaxf(stats[1], norm);
+        if (coef < 1.0f) stats[2] += 1.0f;
+        stats[3] += 1.0f;
+    }
+}
+
+void norm_finalize(at::Tensor partials, long n, double max_norm,
+                   c10::optional<at::Tensor> found_inf, at::Tensor out,
+                   c10::optional<at::Tensor> stats) {
+    TORCH_CHECK(n >= 0 && n < (1L << 31));
+    float* pp = mt_check_partials(partials, (int)n);
+    TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kFloat &&
+                out.is_contiguous() && out.numel() >= 2,
+                "norm_finalize: out must be >=2 contiguous cuda fp32");
+    float* sp = nullptr;
+    if (stats.has_value()) {
+        TORCH_CHECK(stats->is_cuda() && stats->scalar_type() == at::kFloat &&
+                    stats->is_contiguous() && stats->numel() >= 4,
+                    "norm_finalize: stats must be >=4 contiguous cuda fp32");
+        sp = stats->data_ptr<float>();
+    }
+    const float* fi = found_inf.has_value()
+        ? found_inf->data_ptr<float>() : nullptr;
+    auto stream = at::hip::getCurrentHIPStream();
+    hipLaunchKernelGGL(k_mt_norm_finalize, dim3(1), dim3(MT_BLOCK), 0,
+                       stream.stream(), pp, (int)n, (float)max_norm, fi,
+                       out.data_ptr<float>(), sp);
+    HIP_CHECK_LAST();
+}
+
+// g *= *coef in place (the non-lazy clip); no-op when found_inf is set.
+__global__ void k_mt_scale(MTMeta m, const float* __restrict__ coef,
+                           const float* __restrict__ found_inf) {
+    if (found_inf && *found_inf != 0.0f) return;
+    const float c = *coef;
+    int t; long base, end;
+    chunk_range(m, t, base, end);
+    float* g = m.b[t];
+    long vb = base >> 2, ve = end >> 2;
+    for (long i = vb + threadIdx.x; i < ve; i += MT_BLOCK) {
+        f32x4 v = reinterpret_cast<f32x4*>(g)[i];
+        #pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = __fmul_rn(v[j], c);
+        reinterpret_cast<f32x4*>(g)[i] = v;
+    }
+    for (long i = ve * 4 + threadIdx.x; i < end; i += MT_BLOCK)
+        g[i] = __fmul_rn(g[i], c);
+}
+
+void multi_tensor_scale(std::vector<at::Tensor> tensors, at::Tensor coef,
+                        c10::optional<at::Tensor> found_inf) {
+    TORCH_CHECK(coef.is_cuda() && coef.scalar_type() == at::kFloat &&
+                coef.numel() >= 1, "scale: coef must be a cuda fp32 tensor");
+    auto stream = at::hip::getCurrentHIPStream();
+    const float* fi = found_inf.has_value()
+        ? found_inf->data_ptr<float>() : nullptr;
+    for (size_t start = 0; start < tensors.size(); start += MT_MAX) {
+        MTMeta m{};
+        int chunks = 0, nt = 0;
+        for (size_t i = start; i < std::min(tensors.size(), start + MT_MAX); ++i) {
+            auto& g = tensors[i];
+            TORCH_CHECK(g.is_cuda() && g.scalar_type() == at::kFloat &&
+                        g.is_contiguous(), "scale expects contiguous fp32");
+            m.b[nt] = g.data_ptr<float>();
+            m.sizes[nt] = g.numel();
+            m.chunk_start[nt] = chunks;
+            chunks += ceil_div_i(g.numel(), MT_CHUNK);
+            ++nt;
+        }
+        m.chunk_start[nt] = chunks;
+        m.ntensors = nt;
+        if (chunks == 0) continue;
+        hipLaunchKernelGGL(k_mt_scale, dim3(chunks), dim3(MT_BLOCK), 0,
+                           stream.stream(), m, coef.data_ptr<float>(), fi);
         HIP_CHECK_LAST();
     }
 }
@@ -102,9 +334,15 @@ void multi_tensor_unscale(std::vector<at::Tensor> grads, at::Tensor found_inf,
 // buf = mu*buf + g ; d = nesterov ? g + mu*buf : buf ; p -= lr*d
 // With found_inf set, the step is a device-side no-op (amp overflow skip
 // without a host sync).
+// GS: lazy gradient clip — g is read as g * (*grad_scale), rounded once to
+// fp32 before weight decay and the fmaf chain, i.e. bitwise what k_mt_scale
+// followed by the GS=false kernel gives, without rewriting the gradients.
+template <bool GS>
 __global__ void k_mt_sgd(MTMeta m, float lr, float mu, float wd, float nesterov,
-                         const float* __restrict__ found_inf) {
+                         const float* __restrict__ found_inf,
+                         const float* __restrict__ grad_scale) {
     if (found_inf && *found_inf != 0.0f) return;
+    const float gs = GS ? *grad_scale : 1.0f;
     int t; long base, end;
     chunk_range(m, t, base, end);
     const float* __restrict__ g = m.a[t];
@@ -118,6 +356,7 @@ __global__ void k_mt_sgd(MTMeta m, float lr, float mu, float wd, float nesterov,
         #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float gi = gv[j];
+            if (GS) gi = __fmul_rn(gi, gs);
             if (wd != 0.0f) gi = fmaf(wd, pv[j], gi);
             float d = gi;
             if (mu != 0.0f) {
@@ -132,6 +371,7 @@ __global__ void k_mt_sgd(MTMeta m, float lr, float mu, float wd, float nesterov,
     }
     for (long i = ve * 4 + threadIdx.x; i < end; i += MT_BLOCK) {
         float gi = g[i];
+        if (GS) gi = __fmul_rn(gi, gs);
         if (wd != 0.0f) gi = fmaf(wd, p[i], gi);
         float d = gi;
         if (mu != 0.0f) {
@@ -146,13 +386,22 @@ __global__ void k_mt_sgd(MTMeta m, float lr, float mu, float wd, float nesterov,
 void fused_sgd(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
                std::vector<at::Tensor> bufs, double lr, double momentum,
                double wd, double nesterov,
-               c10::optional<at::Tensor> found_inf) {
+               c10::optional<at::Tensor> found_inf,
+               c10::optional<at::Tensor> grad_scale) {
     TORCH_CHECK(params.size() == grads.size());
     bool has_mu = momentum != 0.0;
     TORCH_CHECK(!has_mu || bufs.size() == params.size());
     auto stream = at::hip::getCurrentHIPStream();
     const float* fi = found_inf.has_value()
         ? found_inf->data_ptr<float>() : nullptr;
+    const float* gs = nullptr;
+    if (grad_scale.has_value()) {
+        TORCH_CHECK(grad_scale->is_cuda() &&
+                    grad_scale->scalar_type() == at::kFloat &&
+                    grad_scale->numel() >= 1,
+                    "fused_sgd: grad_scale must be a cuda fp32 tensor");
+        gs = grad_scale->data_ptr<float>();
+    }
     for (size_t start = 0; start < params.size(); start += MT_MAX) {
         MTMeta m{};
         int chunks = 0, nt = 0;
@@ -168,9 +417,15 @@ void fused_sgd(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
         m.chunk_start[nt] = chunks;
         m.ntensors = nt;
         if (chunks == 0) continue;
-        hipLaunchKernelGGL(k_mt_sgd, dim3(chunks), dim3(MT_BLOCK), 0,
-                           stream.stream(), m, (float)lr, (float)momentum,
-                           (float)wd, (float)nesterov, fi);
+        if (gs)
+            hipLaunchKernelGGL(k_mt_sgd<true>, dim3(chunks), dim3(MT_BLOCK), 0,
+                               stream.stream(), m, (float)lr, (float)momentum,
+                               (float)wd, (float)nesterov, fi, gs);
+        else
+            hipLaunchKernelGGL(k_mt_sgd<false>, dim3(chunks), dim3(MT_BLOCK),
+                               0, stream.stream(), m, (float)lr,
+                               (float)momentum, (float)wd, (float)nesterov,
+                               fi, gs);
         HIP_CHECK_LAST();
     }
 }

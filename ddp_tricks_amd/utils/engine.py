@@ -82,6 +82,9 @@ def iterate_loader(
 
     if training:
         amp.maybe_sync_scaler()  # async-amp: fold deferred overflow count
+        if amp.state().max_grad_norm > 0:
+            # gradient-norm telemetry: device-accumulated, one sync per epoch
+            iterate_loader.grad_norm_stats = amp.pop_grad_norm_stats()
     loss = (loss_sum / num).item()
     acc = (correct_sum.double() / num).item()
 

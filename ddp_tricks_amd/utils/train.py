@@ -138,8 +138,10 @@ def train(args):
     early_stopping = EarlyStopping(patience=30, verbose=True)
 
     # amp before DDP wrap (required order — SURVEY Appendix A.12)
+    clip_grad_norm = float(getattr(args, "clip_grad_norm", 0.0) or 0.0)
     model, apex_optimizer = amp.initialize(model, optimizers=lookahead,
-                                           opt_level="O1")
+                                           opt_level="O1",
+                                           max_grad_norm=clip_grad_norm)
     parallel_model = DDP(model)
 
     # Resume from the sidecar checkpoint (extension; the reference saves
@@ -187,6 +189,15 @@ def train(args):
             tb.add_scalars("Loss", {"train": train_loss, "valid": valid_loss}, epoch)
             tb.add_scalars("Acc", {"train": train_acc, "valid": valid_acc}, epoch)
 
+        clip_info = ""
+        if clip_grad_norm > 0:
+            gstats = iterate_loader.grad_norm_stats
+            if local_rank == 0:
+                tb.add_scalar("GradNorm", gstats["mean"], epoch)
+                tb.add_scalar("GradClipFrac", gstats["clipped_frac"], epoch)
+            clip_info = (f", grad_norm: {gstats['mean']:.4f}, "
+                         f"clipped: {100.0 * gstats['clipped_frac']:.1f}%")
+
         phase_info = ""
         # DDPX_PHASE_TIMERS=1; the engine caches PhaseTimers
         # per device (events/streams are device-bound)
@@ -200,7 +211,7 @@ def train(args):
               f"learning_rate: {curr_lr}, "
               f"train_loss: {train_loss:.4f}, train_acc: {train_acc:.4f}, "
               f"valid_loss: {valid_loss:.4f}, valid_acc: {valid_acc:.4f}"
-              f"{phase_info}")
+              f"{phase_info}{clip_info}")
 
         # scheduler gating exactly as the reference (utils/train.py:104-106)
         if epoch <= args.warmup_epochs:

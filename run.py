@@ -47,6 +47,9 @@ def parse_args():
                              "imagenet_synthetic)")
     parser.add_argument("--resume", action="store_true",
                         help="save/load the sidecar resume checkpoint")
+    parser.add_argument("--clip_grad_norm", default=0.0, type=float,
+                        help="clip the global gradient 2-norm to this value "
+                             "(0 = off)")
     args = parser.parse_args()
     if args.local_rank is None:
         args.local_rank = int(os.environ.get("LOCAL_RANK", 0))

@@ -2,6 +2,7 @@
 
 Usage (on a GPU box):  python tools/bench_kernels.py [--resnet]
                        python tools/bench_kernels.py --bn | --bnpool
+                       python tools/bench_kernels.py --clip
 
 Times conv fwd/dgrad/wgrad per shape with HIP events (200 reps after 20
 warmup) and prints achieved TFLOP/s next to microseconds, so kernel A/B
@@ -159,14 +160,112 @@ def bench_bnpool(reps):
         print(f"{name:6s} {'bwd':6s} {us_u:11.1f} {us_f:9.1f}")
 
 
+def _time_alternating(variants, rounds=30, inner=10, warmup=5):
+    """Per-call microseconds of each variant, measured alternately in one
+    process: every round times `inner` back-to-back calls of each variant
+    with device events.  Returns {name: (median, min, max)} over rounds."""
+    for _ in range(warmup):
+        for fn in variants.values():
+            fn()
+    torch.cuda.synchronize()
+    samples = {k: [] for k in variants}
+    for _ in range(rounds):
+        for name, fn in variants.items():
+            s = torch.cuda.Event(enable_timing=True)
+            e = torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(inner):
+                fn()
+            e.record()
+            e.synchronize()
+            samples[name].append(s.elapsed_time(e) / inner * 1000.0)
+    out = {}
+    for k, v in samples.items():
+        v.sort()
+        out[k] = (v[len(v) // 2], v[0], v[-1])
+    return out
+
+
+def bench_clip(rounds):
+    """Gradient-norm clipping: what the fused path adds to the unscale and
+    SGD passes, against the standalone square-sum/finalize/scale passes, at
+    the real gradient payloads (default 4 MiB DDP bucket flats)."""
+    from ddp_tricks_amd.models import build_model
+    from ddp_tricks_amd.parallel.ddp import DistributedDataParallel as DDP
+    ext = load_extension(required=True)
+    dev = torch.device("cuda:0")
+    ch = ext.MT_CHUNK
+    print(f"{'payload':10s} {'MB':>7s} {'variant':26s} {'med us':>9s} "
+          f"{'min':>9s} {'max':>9s}")
+    for name in ("toy_net", "resnet50", "vgg16"):
+        model = build_model(name).to(dev)
+        ddp = DDP(model)
+        flats = ddp.bucket_flats()
+        params = [p for p in model.parameters() if p.requires_grad]
+        for p in params:
+            if p.grad is None:      # grads are views into the bucket flats
+                raise RuntimeError("DDP did not attach bucket-view grads")
+        for f in flats:
+            f.normal_()
+        grads = [p.grad for p in params]
+        bufs = [torch.zeros_like(p) for p in params]
+        n = sum((f.numel() + ch - 1) // ch for f in flats)
+        partials = torch.zeros(n, device=dev)
+        out = torch.zeros(2, device=dev)
+        stats = torch.zeros(4, device=dev)
+        fi = torch.zeros(1, device=dev)
+        one = torch.ones(1, device=dev)
+        mb = sum(f.numel() for f in flats) * 4 / 1e6
+        # inv_scale 1, lr 0, coefficient 1: values stay put over the reps
+
+        def unscale_plain():
+            ext.multi_tensor_unscale(flats, fi, 1.0)
+
+        def unscale_norm():
+            ext.multi_tensor_unscale(flats, fi, 1.0, partials)
+            ext.norm_finalize(partials, n, 1.0, fi, out, stats)
+
+        def sgd_plain():
+            ext.fused_sgd(params, grads, bufs, 0.0, 0.9, 0.0, 1.0, fi)
+
+        def sgd_scaled():
+            ext.fused_sgd(params, grads, bufs, 0.0, 0.9, 0.0, 1.0, fi, one)
+
+        def standalone():
+            ext.multi_tensor_sqsum(flats, partials)
+            ext.norm_finalize(partials, n, 1.0, fi, out, stats)
+            ext.multi_tensor_scale(flats, one, fi)
+
+        res = _time_alternating({
+            "a0 unscale": unscale_plain,
+            "a1 unscale+sqsum+finalize": unscale_norm,
+            "b0 sgd": sgd_plain,
+            "b1 sgd+device scale": sgd_scaled,
+            "c  sqsum+finalize+scale": standalone,
+        }, rounds=rounds)
+        for k, (med, lo, hi) in res.items():
+            print(f"{name:10s} {mb:7.1f} {k:26s} {med:9.1f} {lo:9.1f} "
+                  f"{hi:9.1f}")
+        fused = (res["a1 unscale+sqsum+finalize"][0] - res["a0 unscale"][0]
+                 + res["b1 sgd+device scale"][0] - res["b0 sgd"][0])
+        print(f"{name:10s} {mb:7.1f} fused adds {fused:.1f} us; standalone "
+              f"costs {res['c  sqsum+finalize+scale'][0]:.1f} us")
+        del model, ddp, flats, params, grads, bufs
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--clip", action="store_true")
     ap.add_argument("--resnet", action="store_true")
     ap.add_argument("--functional", action="store_true")
     ap.add_argument("--bn", action="store_true")
     ap.add_argument("--bnpool", action="store_true")
     ap.add_argument("--reps", type=int, default=200)
     args = ap.parse_args()
+    if args.clip:
+        bench_clip(rounds=30)
+        return
     if args.bn:
         bench_bn(args.reps)
         return
