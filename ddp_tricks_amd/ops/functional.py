@@ -215,11 +215,20 @@ def _conv_bwd_impl(ctx, dy):
                 dx = dx[:, :C]
             if x_dtype == torch.float32:
                 dx = dx.float()
+    want_db = has_bias and ctx.needs_input_grad[2]
+    # the wgrad kernels already hold every dy element: with both grads
+    # wanted the bias sums ride along instead of re-reading dy
+    # (DDPX_WGRAD_BIAS=0 restores the separate col_sum pass)
+    fuse_db = (want_db and ctx.needs_input_grad[1]
+               and os.environ.get("DDPX_WGRAD_BIAS", "1") != "0")
     if ctx.needs_input_grad[1]:
-        dw = ext.conv2d_wgrad(dyb, xb, R, S, stride, padding)
+        if fuse_db:
+            dw, db = ext.conv2d_wgrad_bias(dyb, xb, R, S, stride, padding)
+        else:
+            dw = ext.conv2d_wgrad(dyb, xb, R, S, stride, padding)
         if pad8:
             dw = dw[:, :C].contiguous()
-    if has_bias and ctx.needs_input_grad[2]:
+    if want_db and not fuse_db:
         db = ext.col_sum(_nhwc_2d(dyb))
     return dx, dw, db
 

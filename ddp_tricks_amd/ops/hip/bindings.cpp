@@ -99,6 +99,9 @@ std::vector<at::Tensor> conv2d_dgrad_bn(at::Tensor dy, at::Tensor wt2,
                                         at::Tensor bn_invstd);
 at::Tensor conv2d_wgrad(at::Tensor dy, at::Tensor x, long R, long S,
                         long stride, long pad);
+std::vector<at::Tensor> conv2d_wgrad_bias(at::Tensor dy, at::Tensor x,
+                                          long R, long S, long stride,
+                                          long pad);
 
 // comm.cpp
 void register_comm(py::module_& m);
@@ -193,4 +196,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("addend") = c10::nullopt);
     m.def("conv2d_dgrad_bn", &conv2d_dgrad_bn);
     m.def("conv2d_wgrad", &conv2d_wgrad);
+    m.def("conv2d_wgrad_bias", &conv2d_wgrad_bias);
 }

@@ -667,13 +667,29 @@ void k_conv_wgrad(const bf16* __restrict__ dy, const bf16* __restrict__ x,
         }
 }
 
-// combine slab -> dw fp32 in torch KCRS layout (fixed order, deterministic)
+// combine slab -> dw fp32 in torch KCRS layout (fixed order, deterministic).
+// BIAS: the slab carries S x Ko bias partials behind the S dw slices (see
+// k_conv_wgrad_wide_pair) and the launch has one block more: the last block
+// sums those into db while the others do dw (as a second grid-stride trip
+// of the dw blocks the bias sums measured +6 us on conv2's combine).
+template <bool BIAS = false>
 __global__ void k_wgrad_combine(const float* __restrict__ slab, int S,
                                 ConvShape cs, int Kgemm,
-                                float* __restrict__ dw) {
+                                float* __restrict__ dw,
+                                float* __restrict__ db) {
     long total = (long)cs.Ko * Kgemm;
+    const int nb = BIAS ? gridDim.x - 1 : gridDim.x;
+    if (BIAS && (int)blockIdx.x == nb) {
+        const float* bs = slab + (long)S * total;
+        for (int ko = threadIdx.x; ko < cs.Ko; ko += blockDim.x) {
+            float v = 0.f;
+            for (int s = 0; s < S; ++s) v += bs[(long)s * cs.Ko + ko];
+            db[ko] = v;
+        }
+        return;
+    }
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    long stride = (long)gridDim.x * blockDim.x;
+    long stride = (long)nb * blockDim.x;
     int RS = cs.R * cs.S;
     for (; i < total; i += stride) {
         float v = 0.f;
@@ -692,24 +708,32 @@ __global__ void k_wgrad_combine(const float* __restrict__ slab, int S,
 // blocks, each thread chewing 128 dependent 294-KB-strided loads —
 // measured 40.7 us avg where ~38 MB of reads should take <6); this pass
 // runs chunks× more waves and leaves the final KCRS scatter a shallow
-// S/CH-deep sum.
+// S/CH-deep sum.  BIAS: indices past ``total`` do the same for the Ko-wide
+// bias partials, which sit behind the dw slices in both slabs.
+template <bool BIAS = false>
 __global__ void k_wgrad_combine_stage(const float* __restrict__ slab, int S,
-                                      int CH, long total,
+                                      int CH, long total, int Ko,
                                       float* __restrict__ slab2) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
+    if (i >= (BIAS ? total + Ko : total)) return;
     const int c0 = blockIdx.y * CH;
     const int ce = min(S, c0 + CH);
+    long ld = total;
+    if (BIAS && i >= total) {
+        slab += (long)S * total - total;            // -> bias partials
+        slab2 += (long)gridDim.y * total - total;
+        ld = Ko;
+    }
     // two independent accumulator chains (fixed even/odd order — still
     // deterministic) so two loads are in flight per iteration
     float v0 = 0.f, v1 = 0.f;
     int s = c0;
     for (; s + 1 < ce; s += 2) {
-        v0 += slab[(long)s * total + i];
-        v1 += slab[(long)(s + 1) * total + i];
+        v0 += slab[(long)s * ld + i];
+        v1 += slab[(long)(s + 1) * ld + i];
     }
-    if (s < ce) v0 += slab[(long)s * total + i];
-    slab2[(long)blockIdx.y * total + i] = v0 + v1;
+    if (s < ce) v0 += slab[(long)s * ld + i];
+    slab2[(long)blockIdx.y * ld + i] = v0 + v1;
 }
 
 // Single-buffer 32-deep wgrad variant (the pre-pipelining shape; kept for
@@ -1214,7 +1238,15 @@ void k_conv_wgrad_wide_tr(const bf16* __restrict__ dy,
 // Pair-m wide wgrad: each thread stages TWO consecutive m's per j-group so
 // LDS writes are packed b32 (16 stores/operand/iter vs 32 conflicted b16) —
 // the stage phase of the wide kernel is store-issue bound.
-template <int DEPTH = 64>
+//
+// BIAS: the blockIdx.y == 0 blocks (one per (ko tile, split)) also sum the
+// staged dy tile along m straight from lds_a — two threads per ko row, one
+// physical half-row each (a whole-row sum does not care about the XOR
+// swizzle, and tail rows / tail m's are staged as zeros) — and write one
+// bias partial per (split, ko) behind the dw slab, at slab + S*Ko*Kgemm,
+// where the combine kernels pick it up.  The conv's bias gradient then
+// costs no extra pass over dy.  BIAS=false compiles to the kernel it was.
+template <int DEPTH = 64, bool BIAS = false>
 __global__ // NOTE: a 4-waves/SIMD bound (V 78+64A -> 128+0A, occ 3->4) was tried
 // here like k_conv_gemm's and REVERTED: measured 285.7 vs 263.1 us —
 // this kernel's pair-store stage phase wants the AGPR split, not
@@ -1244,6 +1276,7 @@ void k_conv_wgrad_wide_pair(const bf16* __restrict__ dy,
     const int wid = tid >> 6, wr = wid >> 1, wc = wid & 1;
 
     f32x4 acc[4][4] = {};
+    [[maybe_unused]] float bsum = 0.f;
     const int m2 = (tid & (DEPTH / 2 - 1)) * 2;   // m, m+1
     const int jb = (tid / (DEPTH / 2)) * 8;
     constexpr int JSTEP2 = (256 / (DEPTH / 2)) * 8;  // j per pass
@@ -1311,6 +1344,19 @@ void k_conv_wgrad_wide_pair(const bf16* __restrict__ dy,
         }
         __syncthreads();
 
+        if constexpr (BIAS) {
+            if (blockIdx.y == 0) {
+                const bf16* rp = &lds_a[tid >> 1][(tid & 1) * (DEPTH / 2)];
+                #pragma unroll
+                for (int i = 0; i < DEPTH / 2; i += 8) {
+                    bf16x8_t v = *reinterpret_cast<const bf16x8_t*>(rp + i);
+                    #pragma unroll
+                    for (int jj = 0; jj < 8; ++jj)
+                        bsum += us2f((unsigned short)v[jj]);
+                }
+            }
+        }
+
         #pragma unroll
         for (int ks = 0; ks < DEPTH; ks += 32) {
             bf16x8_t af[4], bfr[4];
@@ -1351,6 +1397,16 @@ void k_conv_wgrad_wide_pair(const bf16* __restrict__ dy,
                     acc[mi][ni][r];
             }
         }
+
+    if constexpr (BIAS) {
+        if (blockIdx.y == 0) {
+            bsum += __shfl_xor(bsum, 1, 64);   // the row's other half
+            const int row = ko0 + (tid >> 1);
+            if (!(tid & 1) && row < cs.Ko)
+                slab[(long)S * cs.Ko * Kgemm + (long)split * cs.Ko + row] =
+                    bsum;
+        }
+    }
 }
 
 // conv1 wgrad, fully specialized C==1 / 3x3 (the MNIST stem): each walker
@@ -1359,6 +1415,8 @@ void k_conv_wgrad_wide_pair(const bf16* __restrict__ dy,
 // (q+1 reuses 6 of 9 taps).  dy loads are lane-coalesced along Ko; x loads
 // are wave-uniform scalar broadcasts.  slab layout matches
 // k_wgrad_small_rsc ([k][Ko][split]) so the combine kernel is shared.
+// Since k_wgrad_c1_r3_stream (below) this is the fallback for what that
+// kernel does not take: Ko % 8 != 0.
 __global__ void k_wgrad_c1_r3(const bf16* __restrict__ dy,
                               const bf16* __restrict__ x,
                               float* __restrict__ slab, ConvShape cs,
@@ -1430,6 +1488,102 @@ __global__ void k_wgrad_c1_r3(const bf16* __restrict__ dy,
     }
 }
 
+// Streaming stem wgrad (C == 1, 3x3, Ko % 8 == 0, Ko <= 64).  The walker
+// above moves 128 B per wave instruction with two rows in flight and runs at
+// a tenth of HBM rate; here every lane loads 16 B (8 channels) of dy, so
+// one wave instruction covers RPL = 64 / (Ko/8) consecutive output rows
+// (1 KiB at Ko = 64), and SU independent loads are issued per loop trip.
+// Designed for >= 32 KiB of dy loads in flight per CU: 4 KiB per wave x 8
+// resident waves; at the 3 blocks/CU the register count allows it is 48 KiB.
+// Each lane decodes its own (n, p, q) with the magic divisors (rows of one
+// load may wrap image rows and images) and reads its 3x3 x window with plain
+// cached loads — x is L2-resident.  Per lane: 9 taps x 8 channels of fp32
+// accumulators, plus (BIAS) the plain dy sums as a tenth "tap"; all indices
+// are compile-time.  The end is fixed-order: per tap, the 256 threads park
+// their 8 sums in LDS and thread c < Ko adds the 4 waves x RPL rows of
+// channel c in index order, then writes slab[k][Ko][block] (the layout of
+// k_wgrad_small_rsc, so its combine is shared; tap 9 is db).
+constexpr int SU = 4;
+template <bool BIAS, bool PADDED>
+__global__ __launch_bounds__(256)
+void k_wgrad_c1_r3_stream(const bf16* __restrict__ dy,
+                          const bf16* __restrict__ x,
+                          float* __restrict__ slab, ConvShape cs, long M,
+                          long chunk) {
+    constexpr int NT = BIAS ? 10 : 9;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int lpr = cs.Ko >> 3;            // lanes per dy row
+    const int rpl = 64 / lpr;              // rows per wave load
+    const int r_in = lane / lpr;
+    const int cg = lane - r_in * lpr;
+    const bool lane_on = r_in < rpl;
+    const long w0 = ((long)blockIdx.x * 4 + wave) * chunk;
+    const long w1 = min(M, w0 + chunk);
+    const unsigned short* xs = reinterpret_cast<const unsigned short*>(x);
+    float acc[NT][8] = {};
+    for (long base = w0; base < w1; base += (long)rpl * SU) {
+        bf16x8_t g[SU];
+        long gmv[SU];
+        #pragma unroll
+        for (int u = 0; u < SU; ++u) {
+            const long gm = base + u * rpl + r_in;
+            const bool ok = lane_on && gm < w1;
+            gmv[u] = ok ? gm : -1;
+            // off lanes read row 0 (always there) and are zeroed below
+            g[u] = *reinterpret_cast<const bf16x8_t*>(
+                &dy[(ok ? gm : 0) * cs.Ko + cg * 8]);
+        }
+        #pragma unroll
+        for (int u = 0; u < SU; ++u) {
+            const bool ok = gmv[u] >= 0;
+            const unsigned gm = ok ? (unsigned)gmv[u] : 0u;
+            const unsigned rem = fd_div(gm, cs.fdQ);
+            const int q = (int)fd_mod(gm, cs.fdQ, rem);
+            const int n = (int)fd_div(rem, cs.fdP);
+            const int p = (int)fd_mod(rem, cs.fdP, (unsigned)n);
+            const int h0 = p * cs.stride - cs.pad;
+            const int c0 = q * cs.stride - cs.pad;
+            const long xb = ((long)n * cs.H + h0) * cs.W + c0;
+            float xw[9];
+            #pragma unroll
+            for (int r = 0; r < 3; ++r)
+                #pragma unroll
+                for (int s = 0; s < 3; ++s) {
+                    bool inb = true;
+                    if (PADDED)
+                        inb = h0 + r >= 0 && h0 + r < cs.H &&
+                              c0 + s >= 0 && c0 + s < cs.W;
+                    xw[r * 3 + s] = inb ? us2f(xs[xb + r * cs.W + s]) : 0.f;
+                }
+            #pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float gf = ok ? us2f((unsigned short)g[u][j]) : 0.f;
+                #pragma unroll
+                for (int k = 0; k < 9; ++k)
+                    acc[k][j] = fmaf(gf, xw[k], acc[k][j]);
+                if (BIAS) acc[NT - 1][j] += gf;
+            }
+        }
+    }
+    __shared__ float red[8][256 + 8];   // +8: reader banks rj*8 + rc distinct
+    const int rc = tid >> 3, rj = tid & 7;   // reader: channel rc*8 + rj
+    #pragma unroll
+    for (int k = 0; k < NT; ++k) {
+        __syncthreads();
+        #pragma unroll
+        for (int j = 0; j < 8; ++j) red[j][tid] = acc[k][j];
+        __syncthreads();
+        if (tid < cs.Ko) {
+            float t = 0.f;
+            for (int w = 0; w < 4; ++w)
+                for (int r = 0; r < rpl; ++r)
+                    t += red[rj][w * 64 + r * lpr + rc];
+            slab[((long)k * cs.Ko + tid) * gridDim.x + blockIdx.x] = t;
+        }
+    }
+}
+
 // conv1-style wgrad fast path (RSC <= 16, Ko <= 64): ONE pass over dy per
 // split — all RSC taps accumulate in registers; dy loads are lane-coalesced
 // along Ko, x loads are wave-uniform broadcasts.
@@ -1470,19 +1624,22 @@ __global__ void k_wgrad_small_rsc(const bf16* __restrict__ dy,
     }
 }
 
-// combine for the fast small-RSC path: wave per (k, ko), lanes sweep S
+// combine for the fast small-RSC path: wave per (k, ko), lanes sweep S.
+// With db set the slab has one more "tap", k == RSC: the bias partials.
 __global__ void k_wgrad_small_rsc_combine(const float* __restrict__ slab,
                                           int S, ConvShape cs, int RSC,
-                                          float* __restrict__ dw) {
+                                          float* __restrict__ dw,
+                                          float* __restrict__ db) {
     int i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     int lane = threadIdx.x & 63;
-    if (i >= RSC * cs.Ko) return;
+    if (i >= (RSC + (db != nullptr)) * cs.Ko) return;
     float v = 0.f;
     for (int s = lane; s < S; s += 64) v += slab[(long)i * S + s];
     v = wave_reduce_sum(v);
     if (lane) return;
     int ko = i % cs.Ko;
     int k = i / cs.Ko;
+    if (k == RSC) { db[ko] = v; return; }
     int c = k % cs.C, rs = k / cs.C;
     dw[((long)ko * cs.C + c) * (cs.R * cs.S) + rs] = v;
 }
@@ -1805,8 +1962,16 @@ std::vector<at::Tensor> conv2d_dgrad_bn(at::Tensor dy, at::Tensor wt2,
     return {dx, slab};
 }
 
-at::Tensor conv2d_wgrad(at::Tensor dy, at::Tensor x, long R, long S,
-                        long stride, long pad) {
+at::Tensor col_sum(at::Tensor x);   // gemm.hip
+
+// dw, and with want_bias also db = sum of dy over (n, p, q).  The leaves
+// Toy_Net runs (wide_pair<32>, wide_pair<64>, the streaming stem kernel)
+// produce db inside the wgrad and combine launches; every other leaf takes
+// the separate column-sum pass over dy.
+static std::vector<at::Tensor> wgrad_impl(const at::Tensor& dy,
+                                          const at::Tensor& x, long R,
+                                          long S, long stride, long pad,
+                                          bool want_bias) {
     ConvShape cs = make_shape(x, dy.size(1), (int)R, (int)S, (int)stride,
                               (int)pad);
     TORCH_CHECK(cs.P == dy.size(2) && cs.Q == dy.size(3));
@@ -1817,9 +1982,51 @@ at::Tensor conv2d_wgrad(at::Tensor dy, at::Tensor x, long R, long S,
                         x.options().dtype(at::kFloat));
     const bf16* dyp = reinterpret_cast<const bf16*>(dy.data_ptr());
     const bf16* xp = reinterpret_cast<const bf16*>(x.data_ptr());
+    auto unfused_bias = [&]() -> at::Tensor {
+        if (!want_bias) return at::Tensor();
+        return col_sum(dy.permute({0, 2, 3, 1}).reshape({M, (long)cs.Ko}));
+    };
 
     if (cs.C < 8) {
         int rsc_total = Kgemm;
+        if (cs.C == 1 && cs.R == 3 && cs.S == 3 && cs.Ko % 8 == 0 &&
+            cs.Ko <= 64 && M < INT_MAX) {
+            // work is dealt in wave loads (rpl rows); a block wants >= 2
+            // trips per wave, and 768 blocks = 3 per CU (the occupancy the
+            // kernel's registers allow) all stream at once
+            const int rpl = 64 / (cs.Ko / 8);
+            const long nloads = (M + rpl - 1) / rpl;
+            const int S_ = (int)std::max<long>(
+                1, std::min<long>(768, (nloads + 8 * SU - 1) / (8 * SU)));
+            const long chunk = (nloads + 4L * S_ - 1) / (4L * S_) * rpl;
+            const int nt = want_bias ? 10 : 9;
+            auto slab = at::empty({nt * cs.Ko, S_},
+                                  x.options().dtype(at::kFloat));
+            at::Tensor db;
+            if (want_bias)
+                db = at::empty({(long)cs.Ko}, x.options().dtype(at::kFloat));
+            auto launch = [&](auto kern) {
+                hipLaunchKernelGGL(kern, dim3(S_), dim3(256), 0,
+                                   stream.stream(), dyp, xp,
+                                   slab.data_ptr<float>(), cs, M, chunk);
+            };
+            if (want_bias && cs.pad)
+                launch(k_wgrad_c1_r3_stream<true, true>);
+            else if (want_bias)
+                launch(k_wgrad_c1_r3_stream<true, false>);
+            else if (cs.pad)
+                launch(k_wgrad_c1_r3_stream<false, true>);
+            else
+                launch(k_wgrad_c1_r3_stream<false, false>);
+            HIP_CHECK_LAST();
+            hipLaunchKernelGGL(k_wgrad_small_rsc_combine,
+                               dim3(ceil_div_i(nt * cs.Ko, 4)), dim3(256), 0,
+                               stream.stream(), slab.data_ptr<float>(), S_,
+                               cs, 9, dw.data_ptr<float>(),
+                               want_bias ? db.data_ptr<float>() : nullptr);
+            HIP_CHECK_LAST();
+            return {dw, db};
+        }
         if (rsc_total <= 16 && cs.Ko <= 64) {
             // S=8192 measured slower (164 vs 132 us): per-block reduction
             // fixed costs dominate below ~80 rows/walker
@@ -1839,9 +2046,10 @@ at::Tensor conv2d_wgrad(at::Tensor dy, at::Tensor x, long R, long S,
             hipLaunchKernelGGL(k_wgrad_small_rsc_combine,
                                dim3(ceil_div_i(total, 4)), dim3(256), 0,
                                stream.stream(), slab.data_ptr<float>(), S_,
-                               cs, rsc_total, dw.data_ptr<float>());
+                               cs, rsc_total, dw.data_ptr<float>(),
+                               (float*)nullptr);
             HIP_CHECK_LAST();
-            return dw;
+            return {dw, unfused_bias()};
         }
         int S_ = 64;
         auto slab = at::empty({S_, rsc_total, cs.Ko},
@@ -1857,7 +2065,7 @@ at::Tensor conv2d_wgrad(at::Tensor dy, at::Tensor x, long R, long S,
                            stream.stream(), slab.data_ptr<float>(), S_, cs,
                            rsc_total, dw.data_ptr<float>());
         HIP_CHECK_LAST();
-        return dw;
+        return {dw, unfused_bias()};
     }
 
     TORCH_CHECK(cs.C % 8 == 0 && cs.Ko % 8 == 0);
@@ -1893,20 +2101,41 @@ at::Tensor conv2d_wgrad(at::Tensor dy, at::Tensor x, long R, long S,
     // — 281 vs 174 us at [Ko=64,C=64,M=800k])
     while (gk * gr * S_ < 1024 && S_ < 512 &&
            M / ((long)S_ * 2 * depth) >= 8) S_ *= 2;
-    auto slab = at::empty({S_, (long)cs.Ko, (long)Kgemm},
+    // which leaf runs (same order as the launch chain below)
+    const bool wide_pair = !wv || wv[1] == 'p' || wv[1] == 0;
+    const bool leaf_tr = use_wide && wide64 && wv && wv[1] == 't';
+    const bool leaf_wp32 = !leaf_tr && use_wide &&
+        (wv ? wv[1] == 'q' : !depth64_auto);
+    const bool leaf_wp64 = !leaf_tr && !leaf_wp32 && use_wide && wide64 &&
+        wide_pair;
+    // the wide_pair leaves emit S_ x Ko bias partials behind the dw slices
+    const bool fused_bias = want_bias && (leaf_wp32 || leaf_wp64);
+    const long total = (long)cs.Ko * Kgemm;
+    const long bias_ld = fused_bias ? cs.Ko : 0;
+    auto slab = at::empty({S_ * (total + bias_ld)},
                           x.options().dtype(at::kFloat));
+    at::Tensor db;
+    if (fused_bias)
+        db = at::empty({(long)cs.Ko}, x.options().dtype(at::kFloat));
     // pair-store wide is the measured default (conv4 373 vs 461 us,
     // conv3 165 vs 210); DDPX_WGRAD_V=w selects the scalar-store wide
-    const bool wide_pair = !wv || wv[1] == 'p' || wv[1] == 0;
-    if (use_wide && wide64 && wv && wv[1] == 't')
+    if (leaf_tr)
         hipLaunchKernelGGL(k_conv_wgrad_wide_tr, dim3(gk, gr, S_),
                            dim3(256), 0, stream.stream(), dyp, xp,
                            slab.data_ptr<float>(), cs, M, Kgemm, S_);
-    else if (use_wide && (wv ? wv[1] == 'q' : !depth64_auto))
+    else if (leaf_wp32 && fused_bias)
+        hipLaunchKernelGGL((k_conv_wgrad_wide_pair<32, true>),
+                           dim3(gk, gr, S_), dim3(256), 0, stream.stream(),
+                           dyp, xp, slab.data_ptr<float>(), cs, M, Kgemm, S_);
+    else if (leaf_wp32)
         hipLaunchKernelGGL((k_conv_wgrad_wide_pair<32>), dim3(gk, gr, S_),
                            dim3(256), 0, stream.stream(), dyp, xp,
                            slab.data_ptr<float>(), cs, M, Kgemm, S_);
-    else if (use_wide && wide64 && wide_pair)
+    else if (leaf_wp64 && fused_bias)
+        hipLaunchKernelGGL((k_conv_wgrad_wide_pair<64, true>),
+                           dim3(gk, gr, S_), dim3(256), 0, stream.stream(),
+                           dyp, xp, slab.data_ptr<float>(), cs, M, Kgemm, S_);
+    else if (leaf_wp64)
         hipLaunchKernelGGL((k_conv_wgrad_wide_pair<64>), dim3(gk, gr, S_),
                            dim3(256), 0, stream.stream(), dyp, xp,
                            slab.data_ptr<float>(), cs, M, Kgemm, S_);
@@ -1937,29 +2166,55 @@ at::Tensor conv2d_wgrad(at::Tensor dy, at::Tensor x, long R, long S,
                            stream.stream(), dyp, xp, slab.data_ptr<float>(),
                            cs, M, Kgemm, S_);
     HIP_CHECK_LAST();
-    long total = (long)cs.Ko * Kgemm;
     at::Tensor slab_f = slab;
     int S_c = S_;
+    float* dbp = fused_bias ? db.data_ptr<float>() : nullptr;
     if (S_ > 16) {
         constexpr int CH = 8;
         const int chunks = ceil_div_i(S_, CH);
-        auto slab2 = at::empty({chunks, total},
+        auto slab2 = at::empty({chunks * (total + bias_ld)},
                                x.options().dtype(at::kFloat));
-        const int blocks1 = (int)((total + 255) / 256);
-        hipLaunchKernelGGL(k_wgrad_combine_stage, dim3(blocks1, chunks),
-                           dim3(256), 0, stream.stream(),
-                           slab.data_ptr<float>(), S_, CH, total,
-                           slab2.data_ptr<float>());
+        const int blocks1 = (int)((total + bias_ld + 255) / 256);
+        if (fused_bias)
+            hipLaunchKernelGGL(k_wgrad_combine_stage<true>,
+                               dim3(blocks1, chunks), dim3(256), 0,
+                               stream.stream(), slab.data_ptr<float>(), S_,
+                               CH, total, cs.Ko, slab2.data_ptr<float>());
+        else
+            hipLaunchKernelGGL(k_wgrad_combine_stage<false>,
+                               dim3(blocks1, chunks), dim3(256), 0,
+                               stream.stream(), slab.data_ptr<float>(), S_,
+                               CH, total, cs.Ko, slab2.data_ptr<float>());
         HIP_CHECK_LAST();
         slab_f = slab2;
         S_c = chunks;
     }
     int blocks = std::min<long>(4096, ceil_div_i(total, 256));
-    hipLaunchKernelGGL(k_wgrad_combine, dim3(blocks), dim3(256), 0,
-                       stream.stream(), slab_f.data_ptr<float>(), S_c, cs,
-                       Kgemm, dw.data_ptr<float>());
+    if (fused_bias)
+        hipLaunchKernelGGL(k_wgrad_combine<true>, dim3(blocks + 1),
+                           dim3(256), 0, stream.stream(),
+                           slab_f.data_ptr<float>(), S_c, cs, Kgemm,
+                           dw.data_ptr<float>(), dbp);
+    else
+        hipLaunchKernelGGL(k_wgrad_combine<false>, dim3(blocks), dim3(256),
+                           0, stream.stream(), slab_f.data_ptr<float>(), S_c,
+                           cs, Kgemm, dw.data_ptr<float>(), dbp);
     HIP_CHECK_LAST();
-    return dw;
+    if (want_bias && !fused_bias) db = unfused_bias();
+    return {dw, db};
+}
+
+at::Tensor conv2d_wgrad(at::Tensor dy, at::Tensor x, long R, long S,
+                        long stride, long pad) {
+    return wgrad_impl(dy, x, R, S, stride, pad, false)[0];
+}
+
+// dw as conv2d_wgrad (bit-identical on the MFMA leaves), plus the bias
+// gradient db[ko] = sum over (n, p, q) of dy, fp32
+std::vector<at::Tensor> conv2d_wgrad_bias(at::Tensor dy, at::Tensor x,
+                                          long R, long S, long stride,
+                                          long pad) {
+    return wgrad_impl(dy, x, R, S, stride, pad, true);
 }
 
 

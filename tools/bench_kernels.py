@@ -3,6 +3,7 @@
 Usage (on a GPU box):  python tools/bench_kernels.py [--resnet]
                        python tools/bench_kernels.py --bn | --bnpool
                        python tools/bench_kernels.py --clip
+                       python tools/bench_kernels.py --wgradbias
 
 Times conv fwd/dgrad/wgrad per shape with HIP events (200 reps after 20
 warmup) and prints achieved TFLOP/s next to microseconds, so kernel A/B
@@ -254,9 +255,50 @@ def bench_clip(rounds):
         torch.cuda.empty_cache()
 
 
+def bench_wgradbias(rounds):
+    """Weight + bias gradient of the four Toy_Net convs: conv2d_wgrad
+    followed by col_sum (two passes over dy) against conv2d_wgrad_bias (db
+    out of the wgrad and combine launches), and the wgrad alone."""
+    from ddp_tricks_amd.ops.functional import _nhwc_2d
+    ext = load_extension(required=True)
+    dev = torch.device("cuda:0")
+    print(f"{'shape':8s} {'dy MB':>7s} {'variant':22s} {'med us':>9s} "
+          f"{'min':>9s} {'max':>9s} {'dy TB/s':>8s}")
+    for name, N, C, H, W, K, R, stride, pad in TOYNET:
+        if name == "conv1p8":
+            continue
+        P = (H + 2 * pad - R) // stride + 1
+        x = torch.randn(N, C, H, W, device=dev).to(torch.bfloat16) \
+            .contiguous(memory_format=CL)
+        dy = torch.randn(N, K, P, P, device=dev).to(torch.bfloat16) \
+            .contiguous(memory_format=CL)
+        dy2 = _nhwc_2d(dy)
+        mb = dy.numel() * 2 / 1e6
+
+        def wgrad_only():
+            ext.conv2d_wgrad(dy, x, R, R, stride, pad)
+
+        def unfused():
+            ext.conv2d_wgrad(dy, x, R, R, stride, pad)
+            ext.col_sum(dy2)
+
+        def fused():
+            ext.conv2d_wgrad_bias(dy, x, R, R, stride, pad)
+
+        res = _time_alternating({
+            "wgrad": wgrad_only,
+            "wgrad + col_sum": unfused,
+            "wgrad_bias": fused,
+        }, rounds=rounds)
+        for k, (med, lo, hi) in res.items():
+            print(f"{name:8s} {mb:7.1f} {k:22s} {med:9.1f} {lo:9.1f} "
+                  f"{hi:9.1f} {mb / med:8.2f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clip", action="store_true")
+    ap.add_argument("--wgradbias", action="store_true")
     ap.add_argument("--resnet", action="store_true")
     ap.add_argument("--functional", action="store_true")
     ap.add_argument("--bn", action="store_true")
@@ -265,6 +307,9 @@ def main():
     args = ap.parse_args()
     if args.clip:
         bench_clip(rounds=30)
+        return
+    if args.wgradbias:
+        bench_wgradbias(rounds=30)
         return
     if args.bn:
         bench_bn(args.reps)
