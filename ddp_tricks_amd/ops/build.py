@@ -28,6 +28,7 @@ SOURCES = [
     "bn.hip",
     "gemm.hip",
     "conv.hip",
+    "data.hip",
 ]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

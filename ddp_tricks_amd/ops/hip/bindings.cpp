@@ -103,6 +103,12 @@ std::vector<at::Tensor> conv2d_wgrad_bias(at::Tensor dy, at::Tensor x,
                                           long R, long S, long stride,
                                           long pad);
 
+// data.hip
+std::vector<at::Tensor> batch_gather_aug(at::Tensor store, at::Tensor labels,
+                                         at::Tensor index, at::Tensor lut,
+                                         long pad, bool hflip, long seed,
+                                         long epoch);
+
 // comm.cpp
 void register_comm(py::module_& m);
 
@@ -197,4 +203,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("conv2d_dgrad_bn", &conv2d_dgrad_bn);
     m.def("conv2d_wgrad", &conv2d_wgrad);
     m.def("conv2d_wgrad_bias", &conv2d_wgrad_bias);
+    m.def("batch_gather_aug", &batch_gather_aug,
+          "uint8 HWC device store -> (bf16 channels_last batch, labels): "
+          "gather by index + crop/flip + LUT normalise in one launch",
+          py::arg("store"), py::arg("labels"), py::arg("index"),
+          py::arg("lut"), py::arg("pad"), py::arg("hflip"), py::arg("seed"),
+          py::arg("epoch"));
 }

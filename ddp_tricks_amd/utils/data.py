@@ -13,6 +13,10 @@ torchvision and without network access:
     shuffle, padding to a rank-divisible length, ``set_epoch``.
   * ``CudaPrefetcher`` stages batches pinned and copies H2D on a dedicated
     copy stream one batch ahead (SURVEY N15 disposition).
+  * ``DeviceBatchLoader`` (opt-in) keeps the dataset on the GPU as uint8 and
+    builds each batch — gather, crop, flip, normalise, bf16 channels_last —
+    with one HIP kernel launch (``ops/hip/data.hip``); on CPU it is the
+    reference implementation of the same augmentation.
 """
 from __future__ import annotations
 
@@ -99,6 +103,10 @@ class MNIST(Dataset):
     torchvision.MNIST with ToTensor (reference utils/train.py:25).
     """
 
+    # usual published constants; read only when normalisation is requested
+    MEAN = (0.1307,)
+    STD = (0.3081,)
+
     def __init__(self, root: str = "./datasets/", train: bool = True,
                  download: bool = False, synthetic: Optional[bool] = None,
                  num_samples: Optional[int] = None):
@@ -144,6 +152,9 @@ class CIFAR10(Dataset):
     """CIFAR-10 (synthetic stand-in when the binary batches are absent —
     no network in this environment).  Returns (float32 [3,32,32] in [0,1],
     int64 label); BASELINE.json config 4."""
+
+    MEAN = (0.4914, 0.4822, 0.4465)
+    STD = (0.2470, 0.2435, 0.2616)
 
     @staticmethod
     def _download(root: str) -> None:
@@ -223,6 +234,9 @@ class SyntheticImageNet(Dataset):
     __init__ (per-item generation measured seconds-slow) so the in-memory
     FastBatchLoader path applies.  Size defaults are modest — host RAM is
     ~600 KB/image fp32."""
+
+    MEAN = (0.485, 0.456, 0.406)
+    STD = (0.229, 0.224, 0.225)
 
     def __init__(self, root: str = "./datasets/", train: bool = True,
                  download: bool = False, num_samples: Optional[int] = None):
@@ -422,3 +436,205 @@ class FastBatchLoader:
             dev_i.record_stream(main)
             dev_l.record_stream(main)
             yield dev_i, dev_l
+
+
+# ------------------------------------------------ device-resident datasets ---
+
+_U64 = (1 << 64) - 1
+
+
+def sample_params(seed: int, epoch: int, index, pad: int, hflip: bool):
+    """Per-sample augmentation parameters ``(dx, dy, flip)`` as int64 numpy
+    arrays — the counter hash of ``ops/hip/data.hip`` in numpy ``uint64``
+    (arithmetic modulo 2^64).  Keyed by the DATASET index, so a sample's
+    augmentation in an epoch is independent of batch size, rank and world
+    size and is reproduced by a resumed run."""
+    idx = np.atleast_1d(np.asarray(index)).astype(np.uint64)
+    u = np.uint64
+    s = np.full(1, int(seed) & _U64, dtype=np.uint64)
+    e = np.full(1, int(epoch), dtype=np.uint64)
+    key = (e << u(32)) | idx
+    z = s + (key + u(1)) * u(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> u(30))) * u(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> u(27))) * u(0x94D049BB133111EB)
+    z = z ^ (z >> u(31))
+    span = u(2 * int(pad) + 1)
+    dx = ((z & u(0xFFFF)) * span) >> u(16)
+    dy = (((z >> u(16)) & u(0xFFFF)) * span) >> u(16)
+    flip = ((z >> u(32)) & u(1)) if hflip else np.zeros_like(z)
+    return dx.astype(np.int64), dy.astype(np.int64), flip.astype(np.int64)
+
+
+class Augment:
+    """Augmentation / normalisation config of ``DeviceBatchLoader``.
+
+    ``crop_pad`` = P: random crop of the original size out of the image
+    zero-padded by P pixels (torchvision ``RandomCrop(padding=P)``);
+    ``hflip``: random horizontal flip; ``mean``/``std``: per-channel
+    normalisation.  The kernel does no arithmetic on pixels — everything
+    value-related is folded into the ``[C, 256]`` bf16 table of ``lut()``."""
+
+    def __init__(self, crop_pad: int = 0, hflip: bool = False,
+                 mean=None, std=None):
+        if crop_pad < 0:
+            raise ValueError("crop_pad must be >= 0")
+        if (mean is None) != (std is None):
+            raise ValueError("mean and std go together")
+        self.crop_pad = int(crop_pad)
+        self.hflip = bool(hflip)
+        self.mean = None if mean is None else tuple(float(m) for m in mean)
+        self.std = None if std is None else tuple(float(s) for s in std)
+
+    def lut(self, channels: int) -> torch.Tensor:
+        """[C, 256] bf16 table: value of raw byte u in channel c.  Without
+        mean/std it is (u/255).to(bf16) — bit-for-bit the host path's cast
+        of a k/255 image."""
+        u = torch.arange(256, dtype=torch.float32) / 255.0
+        t = u.unsqueeze(0).repeat(channels, 1)
+        if self.mean is not None:
+            if len(self.mean) != channels or len(self.std) != channels:
+                raise ValueError(
+                    f"mean/std need {channels} entries, got "
+                    f"{len(self.mean)}/{len(self.std)}")
+            mean = torch.tensor(self.mean, dtype=torch.float32).unsqueeze(1)
+            std = torch.tensor(self.std, dtype=torch.float32).unsqueeze(1)
+            t = (t - mean) / std
+        return t.to(torch.bfloat16).contiguous()
+
+    def __repr__(self):
+        return (f"Augment(crop_pad={self.crop_pad}, hflip={self.hflip}, "
+                f"mean={self.mean}, std={self.std})")
+
+
+def quantize_store(images: torch.Tensor, chunk: int = 1024) -> torch.Tensor:
+    """[N,C,H,W] float in [0,1] -> [N,H,W,C] uint8 via round(x*255).  Exact
+    for k/255 images (real MNIST/CIFAR files); anything else — the synthetic
+    stand-ins — is quantised to 8 bits."""
+    N, C, H, W = images.shape
+    store = torch.empty((N, H, W, C), dtype=torch.uint8)
+    for s0 in range(0, N, chunk):
+        q = (images[s0:s0 + chunk].float() * 255.0).round_().clamp_(0, 255)
+        store[s0:s0 + chunk] = q.to(torch.uint8).permute(0, 2, 3, 1)
+    return store
+
+
+def reference_batch(store: torch.Tensor, lut: torch.Tensor,
+                    index: torch.Tensor, pad: int, hflip: bool, seed: int,
+                    epoch: int) -> torch.Tensor:
+    """CPU reference of the ``batch_gather_aug`` kernel: fp32 NCHW batch of
+    ``lut.float()`` values.  Torchvision order (pad, crop, flip): output
+    pixel (y, x) of a sample reads source (y + dy - P, xs + dx - P) with
+    xs = W-1-x when flipped; outside the image the value is lut[c][0]."""
+    N, H, W, C = store.shape
+    index = index.clamp(0, N - 1)          # the kernel clamps too
+    dx, dy, flip = sample_params(seed, epoch, index.numpy(), pad, hflip)
+    dx, dy, flip = (torch.from_numpy(a) for a in (dx, dy, flip))
+    ys = torch.arange(H).unsqueeze(0) + (dy - pad).unsqueeze(1)      # [B,H]
+    xo = torch.arange(W).unsqueeze(0)
+    xo = torch.where(flip.bool().unsqueeze(1), W - 1 - xo, xo)
+    xs = xo + (dx - pad).unsqueeze(1)                                # [B,W]
+    inside = (((ys >= 0) & (ys < H)).unsqueeze(2)
+              & ((xs >= 0) & (xs < W)).unsqueeze(1))                 # [B,H,W]
+    u = store[index.view(-1, 1, 1),
+              ys.clamp(0, H - 1).unsqueeze(2),
+              xs.clamp(0, W - 1).unsqueeze(1)]                       # [B,H,W,C]
+    u = torch.where(inside.unsqueeze(3), u, torch.zeros_like(u)).long()
+    out = lut.float()[torch.arange(C).view(1, 1, 1, C), u]
+    return out.permute(0, 3, 1, 2).contiguous()
+
+
+class DeviceBatchLoader:
+    """Batch loader over a device-resident uint8 copy of an in-memory
+    dataset; same iteration contract as ``FastBatchLoader`` ((images,
+    labels) batches in sampler order, last partial batch kept).
+
+    On a GPU the dataset is quantised once (``round(x*255)``, HWC) and
+    uploaded with its labels; per epoch the sampler's index list goes up as
+    one int64 tensor; per batch ONE launch of ``ext.batch_gather_aug`` on
+    the current stream gathers, crops, flips, normalises and writes the
+    bf16 channels_last batch the stem conv consumes, plus the labels.  No
+    host gather, no H2D copy, no cast/layout pass, no side stream.
+
+    Without a GPU (``device`` None or a CPU device) the same batches come
+    from ``reference_batch`` as fp32 NCHW — the tests' oracle and the CPU
+    training path.
+
+    The device path sees every dataset at 8 bits: real MNIST/CIFAR files
+    (k/255 values) round-trip exactly, the synthetic stand-ins are
+    quantised.  If the store would take more than half of the free device
+    memory the loader prints one line and iterates a ``FastBatchLoader``
+    instead (which cannot augment or normalise)."""
+
+    def __init__(self, dataset, batch_size: int, sampler=None, device=None,
+                 augment: Optional[Augment] = None, seed: int = 0):
+        self.dataset = dataset
+        self.batch_size = batch_size
+        self.sampler = sampler
+        self.device = device
+        self.augment = augment if augment is not None else Augment()
+        self.seed = int(seed)
+        self.gpu = (device is not None and device.type == "cuda"
+                    and torch.cuda.is_available())
+        images = dataset.images
+        N, C, H, W = images.shape
+        self.lut = self.augment.lut(C)
+        self._fallback = None
+        self._ext = None
+        if self.gpu:
+            from ..ops import load_extension
+            self._ext = load_extension(required=True)
+            if self._ext is None:      # DDPX_FORCE_TORCH: no kernel, no loader
+                raise RuntimeError("DeviceBatchLoader needs the _hip_ops "
+                                   "extension on a GPU device")
+            nbytes = N * C * H * W
+            free, _ = torch.cuda.mem_get_info(device)
+            if nbytes > free // 2:
+                print(f"[data] uint8 store of {nbytes / 2**20:.0f} MiB "
+                      f"exceeds half of the free device memory "
+                      f"({free / 2**20:.0f} MiB free); using the host "
+                      f"FastBatchLoader path (no augmentation/normalisation)")
+                self._fallback = FastBatchLoader(
+                    dataset, batch_size, sampler=sampler, pin_memory=True,
+                    device=device)
+                return
+        store = quantize_store(images)
+        labels = dataset.labels.to(torch.int64).contiguous()
+        if self.gpu:
+            self.store = store.to(device)
+            self.labels = labels.to(device)
+            self.lut = self.lut.to(device)
+        else:
+            self.store = store
+            self.labels = labels
+
+    def __len__(self):
+        n = len(self.sampler) if self.sampler is not None else len(self.dataset)
+        return (n + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        if self._fallback is not None:
+            yield from self._fallback
+            return
+        if self.sampler is not None:
+            idx = torch.as_tensor(list(self.sampler), dtype=torch.long)
+        else:
+            idx = torch.arange(len(self.dataset), dtype=torch.long)
+        epoch = int(getattr(self.sampler, "epoch", 0) or 0)
+        aug = self.augment
+        B = self.batch_size
+        if not self.gpu:
+            for s0 in range(0, idx.numel(), B):
+                sel = idx[s0:s0 + B]
+                yield (reference_batch(self.store, self.lut, sel,
+                                       aug.crop_pad, aug.hflip, self.seed,
+                                       epoch),
+                       torch.index_select(self.labels, 0, sel))
+            return
+        idx_dev = idx.to(self.device)     # one upload per epoch
+        seed = self.seed & _U64           # the binding takes it as int64 bits
+        seed = seed - (1 << 64) if seed >> 63 else seed
+        for s0 in range(0, idx.numel(), B):
+            images, labels = self._ext.batch_gather_aug(
+                self.store, self.labels, idx_dev[s0:s0 + B], self.lut,
+                aug.crop_pad, aug.hflip, seed, epoch)
+            yield images, labels

@@ -27,11 +27,17 @@ from ..models import build_model
 from ..ops.optim import FusedSGD
 from ..parallel.ddp import DistributedDataParallel as DDP
 from .callbacks import EarlyStopping, same_seeds
-from .data import DATASETS, DistributedSampler, CudaPrefetcher, FastBatchLoader
+from .data import (DATASETS, Augment, CudaPrefetcher, DeviceBatchLoader,
+                   DistributedSampler, FastBatchLoader)
 from .engine import iterate_loader
 from .lookahead import Lookahead
 from .schedulers import ReduceLROnPlateau, WarmupLambdaLR
 from .tboard import SummaryWriter
+
+
+# --augment choices -> (crop_pad, hflip); crop_flip is the standard CIFAR
+# recipe (random crop with 4-pixel padding + horizontal flip)
+AUGMENT_MODES = {"none": (0, False), "flip": (0, True), "crop_flip": (4, True)}
 
 
 def _resolve_device(local_rank):
@@ -67,7 +73,27 @@ def train(args):
     same_seeds(args.seed_num)
     pin = device.type == "cuda"
     dev_arg = device if pin else None
-    if hasattr(train_set, "images"):   # in-memory tensors: vectorized path
+    # Opt-in device-resident data path (extension): --device_data keeps the
+    # dataset on the GPU as uint8 and builds batches with one HIP kernel;
+    # --augment / --normalize need that loader (the host path can express
+    # neither), so they imply it — on CPU its reference implementation runs.
+    augment_mode = getattr(args, "augment", None) or "none"
+    if augment_mode not in AUGMENT_MODES:
+        raise ValueError(f"unknown augment mode {augment_mode!r}")
+    normalize = bool(getattr(args, "normalize", False))
+    device_data = (bool(getattr(args, "device_data", False))
+                   or augment_mode != "none" or normalize)
+    if device_data and not hasattr(train_set, "images"):
+        raise ValueError("--device_data/--augment/--normalize need an "
+                         "in-memory dataset (one with an .images tensor)")
+    if device_data:
+        norm = dict(mean=Dataset.MEAN, std=Dataset.STD) if normalize else {}
+        crop_pad, hflip = AUGMENT_MODES[augment_mode]
+        train_loader = DeviceBatchLoader(
+            train_set, args.batch_size, sampler=train_sampler,
+            device=dev_arg, seed=args.seed_num,
+            augment=Augment(crop_pad=crop_pad, hflip=hflip, **norm))
+    elif hasattr(train_set, "images"):   # in-memory tensors: vectorized path
         train_loader = FastBatchLoader(train_set, args.batch_size,
                                        sampler=train_sampler, pin_memory=pin,
                                        device=dev_arg)
@@ -88,7 +114,11 @@ def train(args):
               "pair")
         valid_set = Dataset(root=args.data_path, train=False, download=False,
                             synthetic=True)
-    if hasattr(valid_set, "images"):
+    if device_data:    # the valid loader never augments
+        valid_loader = DeviceBatchLoader(valid_set, args.batch_size,
+                                         device=dev_arg, seed=args.seed_num,
+                                         augment=Augment(**norm))
+    elif hasattr(valid_set, "images"):
         valid_loader = FastBatchLoader(valid_set, args.batch_size,
                                        pin_memory=pin, device=dev_arg)
     else:
@@ -97,9 +127,10 @@ def train(args):
     if device.type == "cuda":
         # FastBatchLoader already yields device tensors with its own
         # one-ahead copy stream; only wrap generic DataLoaders
-        if not isinstance(train_loader, FastBatchLoader):
+        own_h2d = (FastBatchLoader, DeviceBatchLoader)
+        if not isinstance(train_loader, own_h2d):
             train_loader = CudaPrefetcher(train_loader, device)
-        if not isinstance(valid_loader, FastBatchLoader):
+        if not isinstance(valid_loader, own_h2d):
             valid_loader = CudaPrefetcher(valid_loader, device)
 
     print(f"Now Training: {args.exp_name}")

@@ -50,6 +50,17 @@ def parse_args():
     parser.add_argument("--clip_grad_norm", default=0.0, type=float,
                         help="clip the global gradient 2-norm to this value "
                              "(0 = off)")
+    parser.add_argument("--device_data", action="store_true",
+                        help="keep the dataset on the GPU as uint8 and build "
+                             "each batch with one fused HIP kernel")
+    parser.add_argument("--augment", default="none", type=str,
+                        choices=("none", "flip", "crop_flip"),
+                        help="train-set augmentation (crop_flip: random crop "
+                             "with 4-pixel padding + horizontal flip); "
+                             "implies --device_data on GPU")
+    parser.add_argument("--normalize", action="store_true",
+                        help="normalise train and valid images with the "
+                             "dataset's per-channel MEAN/STD")
     args = parser.parse_args()
     if args.local_rank is None:
         args.local_rank = int(os.environ.get("LOCAL_RANK", 0))
