@@ -37,6 +37,15 @@ def weight_variant(w: torch.Tensor, variant: str) -> torch.Tensor:
               "nhwc_p8"  — bf16 channels_last with Cin zero-padded to 8
                            (MFMA path for C<8 stems, e.g. ResNet RGB)
               "wt2_p8"   — dgrad operand of the padded weights
+
+    An entry is valid while ``w._version`` is unchanged, so every in-place
+    write to the parameter itself (``w.mul_()``, ``w.copy_()``,
+    ``load_state_dict``, a torch optimizer step) invalidates it.  Writes
+    through ``w.data`` (or ``w.detach()``, or a kernel handed the raw
+    storage) are INVISIBLE here: ``w.data`` carries its own version counter
+    and ``w.data = t`` keeps the old one.  Whoever writes that way must call
+    ``clear_weight_cache()`` afterwards (FusedSGD, Lookahead and the DDP
+    parameter broadcast do).
     """
     ent = _WCACHE.get(w)
     if ent is None or ent["version"] != w._version:

@@ -125,6 +125,10 @@ class DistributedDataParallel(nn.Module):
     # ------------------------------------------------------------- setup ---
 
     def _broadcast_params(self) -> None:
+        # the broadcasts write through p.data, which Tensor._version does
+        # not see: drop any bf16 operand cached by a forward before the wrap
+        from ..ops.functional import clear_weight_cache
+        clear_weight_cache()
         with torch.no_grad():
             if self._rccl is not None:
                 self._ext.rccl_group_start()

@@ -72,6 +72,8 @@ class Lookahead(Optimizer):
         # slow = slow + alpha*(fast - slow) == lerp(slow, fast, alpha)
         torch._foreach_lerp_(slows, fasts, self.alpha)
         torch._foreach_copy_(fasts, slows)
+        from ..ops.functional import clear_weight_cache
+        clear_weight_cache()  # raw writes don't bump _version
 
     def update_lookahead(self) -> None:
         for group in self.param_groups:
