@@ -1066,175 +1066,6 @@ void k_conv_wgrad_sb_pair(const bf16* __restrict__ dy,
         }
 }
 
-// Hardware-transpose wide wgrad: operands stored in NATURAL [m][ko]/[m][rsc]
-// LDS images (16 B ds_write_b128, no software transpose), fragments read
-// with gfx950's ds_read_b64_tr_b16.  Measured semantics (tools/microtests/
-// tr16_probe.hip): within a 16-lane group, lane g's j-th element comes from
-// element (g&3) of the 8-byte chunk at source-lane (4j + (g>>2))'s address;
-// addressing lane g at img[M0 + (g>>2)][col + (g&3)*4] therefore delivers
-// img[M0 + j][col + g] — the exact MFMA fragment.  Row stride 144 elements
-// (128 + 16 pad) makes the 16 addresses bank-disjoint (stride 72 dwords
-// = 8 mod 64).
-constexpr int TRS = 144;           // padded ko/rsc row stride (elements)
-
-typedef __attribute__((address_space(3))) const unsigned short* lds_cptr;
-
-DEV_INLINE unsigned long long tr16_read(lds_cptr a) {
-    unsigned long long r;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(a));
-    return r;
-}
-DEV_INLINE unsigned long long tr16_read_off1152(lds_cptr a) {
-    unsigned long long r;   // +4 m-rows (4 * TRS * 2 bytes = 1152)
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:1152" : "=v"(r) : "v"(a));
-    return r;
-}
-
-__global__ __launch_bounds__(256)
-void k_conv_wgrad_wide_tr(const bf16* __restrict__ dy,
-                          const bf16* __restrict__ x,
-                          float* __restrict__ slab, ConvShape cs, long M,
-                          int Kgemm, int S) {
-    constexpr int DEPTH = 64;
-    __shared__ bf16 img_a[DEPTH][TRS];   // [m][ko]   (natural layout)
-    __shared__ bf16 img_b[DEPTH][TRS];   // [m][rsc]
-    const int ko0 = blockIdx.x * 128;
-    const int rc0 = blockIdx.y * 128;
-    const int split = blockIdx.z;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wid = tid >> 6, wr = wid >> 1, wc = wid & 1;
-
-    f32x4 acc[4][4] = {};
-    const int mloc = tid & 63;
-    const int jq = (tid >> 6) * 8;       // 4 quarters: j = jq + 32h
-
-    const long m_begin = (long)split * DEPTH;
-    for (long mt = m_begin; mt < M; mt += (long)S * DEPTH) {
-        long gm = mt + mloc;
-        const bool valid = gm < M;
-        // ---- A image: dy rows, natural 16 B writes ----
-        #pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            const int j = jq + h * 32;
-            bf16x8_t va = {};
-            if (valid && ko0 + j < cs.Ko)
-                va = *reinterpret_cast<const bf16x8_t*>(
-                    &dy[gm * cs.Ko + ko0 + j]);
-            *reinterpret_cast<bf16x8_t*>(&img_a[mloc][j]) = va;
-        }
-        // ---- B image: im2col(x) gather, natural 16 B writes ----
-        if (valid) {
-            unsigned rem = fd_div((unsigned)gm, cs.fdQ);
-            int q = fd_mod((unsigned)gm, cs.fdQ, rem);
-            unsigned n = fd_div(rem, cs.fdP);
-            int p = fd_mod(rem, cs.fdP, n);
-            #pragma unroll
-            for (int h = 0; h < 4; ++h) {
-                const int j = jq + h * 32;
-                bf16x8_t vb = {};
-                int gk = rc0 + j;
-                if (gk < Kgemm) {
-                    unsigned rs = fd_div(gk, cs.fdC);
-                    int c = fd_mod(gk, cs.fdC, rs);
-                    int r = fd_div(rs, cs.fdS);
-                    int sx = fd_mod(rs, cs.fdS, r);
-                    int hh = p * cs.stride + r - cs.pad;
-                    int wcol = q * cs.stride + sx - cs.pad;
-                    if (hh >= 0 && hh < cs.H && wcol >= 0 && wcol < cs.W)
-                        vb = *reinterpret_cast<const bf16x8_t*>(
-                            &x[(((long)n * cs.H + hh) * cs.W + wcol) * cs.C + c]);
-                }
-                *reinterpret_cast<bf16x8_t*>(&img_b[mloc][j]) = vb;
-            }
-        } else {
-            #pragma unroll
-            for (int h = 0; h < 4; ++h)
-                *reinterpret_cast<bf16x8_t*>(&img_b[mloc][jq + h * 32]) =
-                    bf16x8_t{};
-        }
-        __syncthreads();
-
-        const int g = lane & 15;
-        const int msub = (lane >> 4) * 8 + (g >> 2);   // lane's address row
-        const int csub = (g & 3) * 4;                  // lane's address col
-        #pragma unroll
-        for (int ks = 0; ks < DEPTH; ks += 32) {
-            // issue all 16 transpose reads, wait once, then reinterpret —
-            // asm results are NOT valid until the explicit lgkmcnt wait
-            unsigned long long ra[4][2], rb[4][2];
-            #pragma unroll
-            for (int mi = 0; mi < 4; ++mi) {
-                lds_cptr a = (lds_cptr)&img_a[ks + msub]
-                                            [wr * 64 + mi * 16 + csub];
-                ra[mi][0] = tr16_read(a);
-                ra[mi][1] = tr16_read_off1152(a);
-            }
-            #pragma unroll
-            for (int ni = 0; ni < 4; ++ni) {
-                lds_cptr b = (lds_cptr)&img_b[ks + msub]
-                                            [wc * 64 + ni * 16 + csub];
-                rb[ni][0] = tr16_read(b);
-                rb[ni][1] = tr16_read_off1152(b);
-            }
-            // counted waits: start the ni-th MFMA column as soon as its
-            // B fragment lands; the waited values are threaded THROUGH the
-            // asm ("+v") so the compiler cannot reorder their uses above it
-            bf16x8_t af[4], bfr[4];
-            asm volatile("s_waitcnt lgkmcnt(6)"
-                         : "+v"(ra[0][0]), "+v"(ra[0][1]), "+v"(ra[1][0]),
-                           "+v"(ra[1][1]), "+v"(ra[2][0]), "+v"(ra[2][1]),
-                           "+v"(ra[3][0]), "+v"(ra[3][1]), "+v"(rb[0][0]),
-                           "+v"(rb[0][1]));
-            #pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-                __builtin_memcpy(&af[mi], &ra[mi][0], 16);
-            __builtin_memcpy(&bfr[0], &rb[0][0], 16);
-            #pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-                acc[mi][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                    af[mi], bfr[0], acc[mi][0], 0, 0, 0);
-            asm volatile("s_waitcnt lgkmcnt(4)"
-                         : "+v"(rb[1][0]), "+v"(rb[1][1]));
-            __builtin_memcpy(&bfr[1], &rb[1][0], 16);
-            #pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-                acc[mi][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                    af[mi], bfr[1], acc[mi][1], 0, 0, 0);
-            asm volatile("s_waitcnt lgkmcnt(2)"
-                         : "+v"(rb[2][0]), "+v"(rb[2][1]));
-            __builtin_memcpy(&bfr[2], &rb[2][0], 16);
-            #pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-                acc[mi][2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                    af[mi], bfr[2], acc[mi][2], 0, 0, 0);
-            asm volatile("s_waitcnt lgkmcnt(0)"
-                         : "+v"(rb[3][0]), "+v"(rb[3][1]));
-            __builtin_memcpy(&bfr[3], &rb[3][0], 16);
-            #pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-                acc[mi][3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                    af[mi], bfr[3], acc[mi][3], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-
-    #pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-        #pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-            int col = rc0 + wc * 64 + ni * 16 + (lane & 15);
-            if (col >= Kgemm) continue;
-            #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                int row = ko0 + wr * 64 + mi * 16 + (lane >> 4) * 4 + r;
-                if (row >= cs.Ko) continue;
-                slab[((long)split * cs.Ko + row) * Kgemm + col] =
-                    acc[mi][ni][r];
-            }
-        }
-}
-
 // Pair-m wide wgrad: each thread stages TWO consecutive m's per j-group so
 // LDS writes are packed b32 (16 stores/operand/iter vs 32 conflicted b16) —
 // the stage phase of the wide kernel is store-issue bound.
@@ -1405,6 +1236,225 @@ void k_conv_wgrad_wide_pair(const bf16* __restrict__ dy,
             if (!(tid & 1) && row < cs.Ko)
                 slab[(long)S * cs.Ko * Kgemm + (long)split * cs.Ko + row] =
                     bsum;
+        }
+    }
+}
+
+// fd_div as a select, not a branch: keeps wide_dma's per-tile address block
+// one straight run of VALU the scheduler can place under the DMA wait
+DEV_INLINE unsigned fd_div_sel(unsigned n, FastDiv f) {
+    unsigned hi = (unsigned)(((unsigned long long)n * f.mul) >> 32);
+    return (f.mul == 0 ? n : hi) >> f.shift;
+}
+
+typedef short tr16x4_t __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) tr16x4_t* lds_tr16_ptr;
+
+// LDS-DMA staged wide wgrad: k_conv_wgrad_wide_pair's grid, slab layout,
+// split order, 2x2 waves of 64x64 and k->m mapping, but the forward kernel's
+// staging.  Both operands are m-major in memory, so 16 B global_load_lds
+// fills NATURAL images img_a[m][ko] / img_b[m][rsc] (no VGPR round trip, no
+// pack VALU, no ds_write) and the MFMA fragments (m contiguous per lane) come
+// from gfx950's transposed read ds_read_b64_tr_b16: within a 16-lane group,
+// lane g addresses img[M0 + (g>>2)][col + (g&3)*4] and receives
+// img[M0 + j][col + g], j = 0..3 (tools/microtests/tr16_probe.hip); a
+// fragment is two reads 4 rows apart.  The instruction needs EXEC all ones:
+// nothing lane-divergent encloses the read + MFMA block.
+//
+// Rows are 256 B, so every row starts on bank 0.  The 32 lanes of one read
+// service group touch rows M0+{0..3} and M0+8+{0..3}, 32 B each; the 16 B
+// segments are XOR-swizzled with 2*((row&3) | ((row>>3)&1)<<2), which puts
+// those eight 32 B pieces on eight disjoint bank octets.  glds writes
+// lane-linear, so the swizzle sits on the per-lane SOURCE address and is
+// repeated on the reads (rule 21, as conv_gemm_body).  The value is the same
+// for row and row+4 (the second half-fragment is an immediate offset) and,
+// for the staging lanes, the same for every chunk a lane fills: a lane's
+// logical segment never changes, so its (ko) and (r, s, c) decode runs once.
+// Out-of-range lanes (m >= M, ko >= Ko, rsc >= Kgemm, padding taps) read
+// g_zero16; no lane hands the DMA an address outside dy or x.
+//
+// Same split, depth, zero fills and MFMA order as wide_pair, so dw is
+// bit-identical to that leaf.  BIAS: blockIdx.y == 0 blocks sum img_a along
+// m with eight accumulators per ko, DEPTH/8 rows of every tile each, joined
+// serially at the end: a chain of tiles*DEPTH/8 + 7 additions, inside the
+// tiles*DEPTH/2 + 1 that the bound in tests/test_gpu_wgrad_bias.py assumes.
+//
+// Register bound: 3 blocks/CU measured best.  Left free, the compiler
+// splits 64 accumulators into AGPRs and DEPTH 64 lands at 2 waves/SIMD
+// (114+64A): conv3 122.6 vs 111.1 us, conv4 254.3 vs 221.9.  DEPTH 32 ties
+// with the bound free (conv2 217.7 vs 216.2).  Only DEPTH 64 computes the
+// next tile's addresses ahead (AHEAD): DEPTH 32 under a 4-block bound
+// spilled with it, and was not tried again at 3.
+template <int DEPTH = 64, bool BIAS = false>
+__global__ __launch_bounds__(256, 3)
+void k_conv_wgrad_wide_dma(const bf16* __restrict__ dy,
+                           const bf16* __restrict__ x,
+                           float* __restrict__ slab, ConvShape cs, long M,
+                           int Kgemm, int S) {
+    __shared__ __align__(16) bf16 img_a[DEPTH][128];   // [m][ko]
+    __shared__ __align__(16) bf16 img_b[DEPTH][128];   // [m][rsc]
+    constexpr int NCH = DEPTH / 16;   // 4-row glds chunks per wave per image
+    constexpr bool AHEAD = DEPTH == 64;
+    const int ko0 = blockIdx.x * 128;
+    const int rc0 = blockIdx.y * 128;
+    const int split = blockIdx.z;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wid = tid >> 6, wr = wid >> 1, wc = wid & 1;
+
+    // ---- staging: wave wid fills chunks wid + 4i, rows 4*chunk + srow ----
+    const int srow = lane >> 4;
+    const int lseg = (lane & 15) ^ (2 * (srow | (((wid >> 1) & 1) << 2)));
+    const int a_ko = ko0 + lseg * 8;
+    const bool a_ok = a_ko < cs.Ko;
+    const int b_gk = rc0 + lseg * 8;
+    const bool b_ok = b_gk < Kgemm;
+    int b_c = 0, b_dh = 0, b_dw = 0;
+    if (b_ok) {
+        unsigned rs = fd_div(b_gk, cs.fdC);
+        b_c = fd_mod(b_gk, cs.fdC, rs);
+        unsigned r = fd_div(rs, cs.fdS);
+        b_dw = (int)fd_mod(rs, cs.fdS, r) - cs.pad;
+        b_dh = (int)r - cs.pad;
+    }
+    const bf16* const zsrc = reinterpret_cast<const bf16*>(g_zero16);
+    const bf16* sa[NCH];
+    const bf16* sb[NCH];
+    auto sources = [&](long mt) {
+        #pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            // branch-free: index arithmetic on an out-of-range row is
+            // harmless, only the final select decides what is dereferenced
+            const long gm = mt + (wid + 4 * i) * 4 + srow;
+            const bool m_ok = gm < M;
+            unsigned rem = fd_div_sel((unsigned)gm, cs.fdQ);
+            int q = fd_mod((unsigned)gm, cs.fdQ, rem);
+            unsigned n = fd_div_sel(rem, cs.fdP);
+            int p = fd_mod(rem, cs.fdP, n);
+            int h = p * cs.stride + b_dh;
+            int wcol = q * cs.stride + b_dw;
+            const bool x_ok = m_ok & b_ok & (h >= 0) & (h < cs.H) &
+                              (wcol >= 0) & (wcol < cs.W);
+            const long oa = gm * cs.Ko + a_ko;
+            const long ob = (((long)n * cs.H + h) * cs.W + wcol) * cs.C + b_c;
+            sa[i] = (m_ok & a_ok) ? dy + oa : zsrc;
+            sb[i] = x_ok ? x + ob : zsrc;
+        }
+    };
+
+    // ---- fragment reads: element offsets, constant over tiles ----
+    const int g = lane & 15;
+    const int rsw = 2 * ((g >> 2) | (((lane >> 4) & 1) << 2));
+    const int rbase = ((lane >> 4) * 8 + (g >> 2)) * 128 + (g & 1) * 4;
+    const int rseg = (g & 3) >> 1;
+    int offa[4], offb[4];
+    #pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        offa[i] = rbase + ((wr * 8 + i * 2 + rseg) ^ rsw) * 8;
+        offb[i] = rbase + ((wc * 8 + i * 2 + rseg) ^ rsw) * 8;
+    }
+    auto frag = [](const bf16* p) {
+        tr16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+            (lds_tr16_ptr)p);
+        tr16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+            (lds_tr16_ptr)(p + 4 * 128));
+        return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+    };
+
+    f32x4 acc[4][4] = {};
+    [[maybe_unused]] float bsum[4] = {};
+    const long m_begin = (long)split * DEPTH;
+    const long m_step = (long)S * DEPTH;
+    if (AHEAD && m_begin < M) sources(m_begin);
+
+    for (long mt = m_begin; mt < M; mt += m_step) {
+        if (!AHEAD) sources(mt);
+        #pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            __builtin_amdgcn_global_load_lds(
+                (const __attribute__((address_space(1))) unsigned short*)sa[i],
+                (__attribute__((address_space(3))) unsigned short*)
+                    &img_a[(wid + 4 * i) * 4][0], 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(
+                (const __attribute__((address_space(1))) unsigned short*)sb[i],
+                (__attribute__((address_space(3))) unsigned short*)
+                    &img_b[(wid + 4 * i) * 4][0], 16, 0, 0);
+        }
+        // next tile's addresses while this tile's DMA is in flight
+        if (AHEAD && mt + m_step < M) sources(mt + m_step);
+        __syncthreads();   // vmcnt(0) for the in-flight glds + barrier
+
+        if constexpr (BIAS) {
+            if (blockIdx.y == 0) {
+                // thread = (row group tid>>5, ko quad tid&31): 8 B reads of
+                // the group's DEPTH/8 rows (the swizzle moves whole 16 B
+                // segments, so a quad stays contiguous)
+                const int kq = tid & 31;
+                const bf16* rp = &img_a[(tid >> 5) * (DEPTH / 8)][(kq & 1) * 4];
+                #pragma unroll
+                for (int i = 0; i < DEPTH / 8; ++i) {
+                    // row = (tid>>5)*(DEPTH/8) + i: its swizzle bits
+                    const int row = (tid >> 5) * (DEPTH / 8) + i;
+                    const int sw = 2 * ((row & 3) | (((row >> 3) & 1) << 2));
+                    s16x4 v = *reinterpret_cast<const s16x4*>(
+                        rp + i * 128 + (((kq >> 1) ^ sw) << 3));
+                    #pragma unroll
+                    for (int jj = 0; jj < 4; ++jj)
+                        bsum[jj] += us2f((unsigned short)v[jj]);
+                }
+            }
+        }
+
+        #pragma unroll
+        for (int ks = 0; ks < DEPTH; ks += 32) {
+            bf16x8_t af[4], bfr[4];
+            #pragma unroll
+            for (int mi = 0; mi < 4; ++mi)
+                af[mi] = frag(&img_a[ks][0] + offa[mi]);
+            #pragma unroll
+            for (int ni = 0; ni < 4; ++ni)
+                bfr[ni] = frag(&img_b[ks][0] + offb[ni]);
+            #pragma unroll
+            for (int mi = 0; mi < 4; ++mi)
+                #pragma unroll
+                for (int ni = 0; ni < 4; ++ni)
+                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        af[mi], bfr[ni], acc[mi][ni], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+
+    #pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+        #pragma unroll
+        for (int ni = 0; ni < 4; ++ni) {
+            int col = rc0 + wc * 64 + ni * 16 + (lane & 15);
+            if (col >= Kgemm) continue;
+            #pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                int row = ko0 + wr * 64 + mi * 16 + (lane >> 4) * 4 + r;
+                if (row >= cs.Ko) continue;
+                slab[((long)split * cs.Ko + row) * Kgemm + col] =
+                    acc[mi][ni][r];
+            }
+        }
+
+    if constexpr (BIAS) {
+        if (blockIdx.y == 0) {
+            // join the two half-tile chains (the loop's last barrier has
+            // retired every read of img_a)
+            float* join = reinterpret_cast<float*>(&img_a[0][0]);  // [8][128]
+            #pragma unroll
+            for (int jj = 0; jj < 4; ++jj)
+                join[(tid >> 5) * 128 + (tid & 31) * 4 + jj] = bsum[jj];
+            __syncthreads();
+            const int row = ko0 + tid;
+            if (tid < 128 && row < cs.Ko) {
+                float s = join[tid];
+                #pragma unroll
+                for (int gi = 1; gi < 8; ++gi) s += join[gi * 128 + tid];
+                slab[(long)S * cs.Ko * Kgemm + (long)split * cs.Ko + row] = s;
+            }
         }
     }
 }
@@ -1965,7 +2015,7 @@ std::vector<at::Tensor> conv2d_dgrad_bn(at::Tensor dy, at::Tensor wt2,
 at::Tensor col_sum(at::Tensor x);   // gemm.hip
 
 // dw, and with want_bias also db = sum of dy over (n, p, q).  The leaves
-// Toy_Net runs (wide_pair<32>, wide_pair<64>, the streaming stem kernel)
+// Toy_Net runs (wide_dma<32>, wide_dma<64>, the streaming stem kernel)
 // produce db inside the wgrad and combine launches; every other leaf takes
 // the separate column-sum pass over dy.
 static std::vector<at::Tensor> wgrad_impl(const at::Tensor& dy,
@@ -2070,13 +2120,15 @@ static std::vector<at::Tensor> wgrad_impl(const at::Tensor& dy,
 
     TORCH_CHECK(cs.C % 8 == 0 && cs.Ko % 8 == 0);
     // Variant choice is MEASURED (profiles/, tools/bench_kernels.py):
-    //   * 128x128 pair-store wide tile, 64-deep, for big-Kgemm convs with
-    //     enough tiles (conv3 165, conv4 373 us);
+    //   * 128x128 wide tile, LDS-DMA staged (k_conv_wgrad_wide_dma),
+    //     64-deep, for big-Kgemm convs with enough tiles (with bias: conv3
+    //     119 vs 174 us pair-store, conv4 235 vs 384);
     //   * the same tile 32-DEEP for small-Kgemm or tile-starved-but-deep-M
-    //     shapes (conv2 308 vs 345 sb; [1024ch 1x1] 76 vs 95 us) — the
-    //     shallower stage runs at occupancy 4 vs 3;
+    //     shapes (conv2 218 vs 282 us pair-store);
     //   * 64x64 pair-store sb otherwise.  DDPX_WGRAD_V overrides
-    //     (w/wq/w3/wx/wt/s/s6/sx/p).
+    //     (w/wp/wq/w3/wx/wt/wt3/s/s6/sx/p); wp / wq are the pair-store
+    //     wide leaves the DMA leaf replaced (profiles/
+    //     toynet_b1024_1gpu_kernel_stats_wgraddma.md).
     static const char* wv = getenv("DDPX_WGRAD_V");
     const char sel = wv ? wv[0] : 0;
     const bool can_wide = cs.Ko >= 128 && Kgemm >= 128;
@@ -2103,13 +2155,18 @@ static std::vector<at::Tensor> wgrad_impl(const at::Tensor& dy,
            M / ((long)S_ * 2 * depth) >= 8) S_ *= 2;
     // which leaf runs (same order as the launch chain below)
     const bool wide_pair = !wv || wv[1] == 'p' || wv[1] == 0;
-    const bool leaf_tr = use_wide && wide64 && wv && wv[1] == 't';
-    const bool leaf_wp32 = !leaf_tr && use_wide &&
+    // LDS-DMA staged leaf: the automatic choice for both wide classes;
+    // wt = the same by letter, wt3 = forced 32-deep
+    const bool leaf_dma = use_wide && (!wv || wv[1] == 't');
+    const bool leaf_dma32 = leaf_dma &&
+        ((wv && wv[2] == '3') || !depth64_auto);
+    const bool leaf_wp32 = !leaf_dma && use_wide &&
         (wv ? wv[1] == 'q' : !depth64_auto);
-    const bool leaf_wp64 = !leaf_tr && !leaf_wp32 && use_wide && wide64 &&
+    const bool leaf_wp64 = !leaf_dma && !leaf_wp32 && use_wide && wide64 &&
         wide_pair;
-    // the wide_pair leaves emit S_ x Ko bias partials behind the dw slices
-    const bool fused_bias = want_bias && (leaf_wp32 || leaf_wp64);
+    // the wide_pair and wide_dma leaves emit S_ x Ko bias partials behind
+    // the dw slices
+    const bool fused_bias = want_bias && (leaf_wp32 || leaf_wp64 || leaf_dma);
     const long total = (long)cs.Ko * Kgemm;
     const long bias_ld = fused_bias ? cs.Ko : 0;
     auto slab = at::empty({S_ * (total + bias_ld)},
@@ -2117,10 +2174,22 @@ static std::vector<at::Tensor> wgrad_impl(const at::Tensor& dy,
     at::Tensor db;
     if (fused_bias)
         db = at::empty({(long)cs.Ko}, x.options().dtype(at::kFloat));
-    // pair-store wide is the measured default (conv4 373 vs 461 us,
-    // conv3 165 vs 210); DDPX_WGRAD_V=w selects the scalar-store wide
-    if (leaf_tr)
-        hipLaunchKernelGGL(k_conv_wgrad_wide_tr, dim3(gk, gr, S_),
+    // DDPX_WGRAD_V=wp/wq select the pair-store wide (conv4 373 vs 461 us,
+    // conv3 165 vs 210 against the scalar-store wide that plain w3/wx run)
+    if (leaf_dma32 && fused_bias)
+        hipLaunchKernelGGL((k_conv_wgrad_wide_dma<32, true>),
+                           dim3(gk, gr, S_), dim3(256), 0, stream.stream(),
+                           dyp, xp, slab.data_ptr<float>(), cs, M, Kgemm, S_);
+    else if (leaf_dma32)
+        hipLaunchKernelGGL((k_conv_wgrad_wide_dma<32>), dim3(gk, gr, S_),
+                           dim3(256), 0, stream.stream(), dyp, xp,
+                           slab.data_ptr<float>(), cs, M, Kgemm, S_);
+    else if (leaf_dma && fused_bias)
+        hipLaunchKernelGGL((k_conv_wgrad_wide_dma<64, true>),
+                           dim3(gk, gr, S_), dim3(256), 0, stream.stream(),
+                           dyp, xp, slab.data_ptr<float>(), cs, M, Kgemm, S_);
+    else if (leaf_dma)
+        hipLaunchKernelGGL((k_conv_wgrad_wide_dma<64>), dim3(gk, gr, S_),
                            dim3(256), 0, stream.stream(), dyp, xp,
                            slab.data_ptr<float>(), cs, M, Kgemm, S_);
     else if (leaf_wp32 && fused_bias)

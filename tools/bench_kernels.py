@@ -4,6 +4,7 @@ Usage (on a GPU box):  python tools/bench_kernels.py [--resnet]
                        python tools/bench_kernels.py --bn | --bnpool
                        python tools/bench_kernels.py --clip
                        python tools/bench_kernels.py --wgradbias
+                       python tools/bench_kernels.py --wgraddma [--leaves wt3]
 
 Times conv fwd/dgrad/wgrad per shape with HIP events (200 reps after 20
 warmup) and prints achieved TFLOP/s next to microseconds, so kernel A/B
@@ -295,10 +296,121 @@ def bench_wgradbias(rounds):
                   f"{hi:9.1f} {mb / med:8.2f}")
 
 
+def _wgraddma_child():
+    """One leaf's side of --wgraddma: DDPX_WGRAD_V is read once per
+    process, so each leaf lives in a process of its own.  Protocol on
+    stdin/stdout, one line each way: ``setup <shape index>`` allocates the
+    operands and warms up, ``run <0|1> <inner>`` answers the per-call
+    microseconds of `inner` back-to-back calls (1 = with bias), ``quit``."""
+    ext = load_extension(required=True)
+    dev = torch.device("cuda:0")
+    x = dy = geo = None
+    for line in sys.stdin:
+        cmd = line.split()
+        if not cmd or cmd[0] == "quit":
+            break
+        if cmd[0] == "setup":
+            name, N, C, H, W, K, R, stride, pad = TOYNET[int(cmd[1])]
+            P = (H + 2 * pad - R) // stride + 1
+            g = torch.Generator(device=dev).manual_seed(0)
+            x = torch.randn(N, C, H, W, device=dev, generator=g) \
+                .to(torch.bfloat16).contiguous(memory_format=CL)
+            dy = torch.randn(N, K, P, P, device=dev, generator=g) \
+                .to(torch.bfloat16).contiguous(memory_format=CL)
+            geo = (R, R, stride, pad)
+            for _ in range(5):
+                ext.conv2d_wgrad(dy, x, *geo)
+                ext.conv2d_wgrad_bias(dy, x, *geo)
+            torch.cuda.synchronize()
+            print("ok", flush=True)
+            continue
+        fn = ext.conv2d_wgrad_bias if cmd[1] == "1" else ext.conv2d_wgrad
+        inner = int(cmd[2])
+        s = torch.cuda.Event(enable_timing=True)
+        e = torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(inner):
+            fn(dy, x, *geo)
+        e.record()
+        e.synchronize()
+        print(f"{s.elapsed_time(e) / inner * 1000.0:.3f}", flush=True)
+
+
+def bench_wgraddma(rounds, extra, inner=10):
+    """wgrad of the four Toy_Net convs, with and without bias: the
+    wide_pair leaf of the shape's depth class (wp / wq) against the LDS-DMA
+    staged leaf (wt), plus any further DDPX_WGRAD_V letters in `extra`.
+    Every leaf runs in a fresh child process; rounds alternate between the
+    children, device events around `inner` calls, median/min/max over
+    `rounds`.  This process never opens the GPU.  conv1 (C = 1) takes the
+    stem kernel under every letter: it is the control row."""
+    import subprocess
+    leaves = ["wp", "wq", "wt"] + [v for v in extra if v]
+    kids = {}
+    for leaf in leaves:
+        env = dict(os.environ)
+        env["DDPX_WGRAD_V"] = leaf
+        kids[leaf] = subprocess.Popen(
+            [sys.executable, os.path.abspath(__file__), "--wgraddma-child"],
+            env=env, stdin=subprocess.PIPE, stdout=subprocess.PIPE,
+            text=True, bufsize=1)
+
+    def ask(leaf, msg):
+        kids[leaf].stdin.write(msg + "\n")
+        kids[leaf].stdin.flush()
+        ans = kids[leaf].stdout.readline().strip()
+        if not ans:
+            raise RuntimeError(f"child {leaf} died on '{msg}'")
+        return ans
+
+    try:
+        print(f"{'shape':8s} {'bias':>4s} {'leaf':6s} {'med us':>9s} "
+              f"{'min':>9s} {'max':>9s} {'TFLOP/s':>8s}")
+        for idx, (name, N, C, H, W, K, R, stride, pad) in enumerate(TOYNET):
+            if name == "conv1p8":
+                continue
+            P = (H + 2 * pad - R) // stride + 1
+            flops = 2.0 * N * P * P * K * C * R * R
+            old = "wp" if R * R * C >= 1152 else "wq"
+            use = [v for v in leaves if v not in ("wp", "wq") or v == old]
+            for leaf in use:
+                ask(leaf, f"setup {idx}")
+            for bias in (0, 1):
+                samples = {v: [] for v in use}
+                for _ in range(rounds):
+                    for leaf in use:
+                        samples[leaf].append(
+                            float(ask(leaf, f"run {bias} {inner}")))
+                for leaf in use:
+                    v = sorted(samples[leaf])
+                    med = v[len(v) // 2]
+                    print(f"{name:8s} {bias:4d} {leaf:6s} {med:9.1f} "
+                          f"{v[0]:9.1f} {v[-1]:9.1f} {flops / med / 1e6:8.1f}",
+                          flush=True)
+    finally:
+        for p in kids.values():
+            try:
+                p.stdin.write("quit\n")
+                p.stdin.close()
+            except OSError:
+                pass
+        for p in kids.values():
+            try:
+                p.wait(timeout=30)
+            except subprocess.TimeoutExpired:
+                p.kill()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clip", action="store_true")
     ap.add_argument("--wgradbias", action="store_true")
+    ap.add_argument("--wgraddma", action="store_true")
+    ap.add_argument("--wgraddma-child", action="store_true",
+                    help=argparse.SUPPRESS)
+    ap.add_argument("--leaves", default="",
+                    help="further DDPX_WGRAD_V letters for --wgraddma, "
+                         "comma separated (e.g. wt3)")
     ap.add_argument("--resnet", action="store_true")
     ap.add_argument("--functional", action="store_true")
     ap.add_argument("--bn", action="store_true")
@@ -310,6 +422,12 @@ def main():
         return
     if args.wgradbias:
         bench_wgradbias(rounds=30)
+        return
+    if args.wgraddma_child:
+        _wgraddma_child()
+        return
+    if args.wgraddma:
+        bench_wgraddma(rounds=30, extra=args.leaves.split(","))
         return
     if args.bn:
         bench_bn(args.reps)
