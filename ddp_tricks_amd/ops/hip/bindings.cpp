@@ -102,6 +102,9 @@ at::Tensor conv2d_wgrad(at::Tensor dy, at::Tensor x, long R, long S,
 std::vector<at::Tensor> conv2d_wgrad_bias(at::Tensor dy, at::Tensor x,
                                           long R, long S, long stride,
                                           long pad);
+std::tuple<std::string, long, bool> conv2d_wgrad_plan(
+    long N, long C, long H, long W, long Ko, long R, long S, long stride,
+    long pad, bool want_bias);
 
 // data.hip
 std::vector<at::Tensor> batch_gather_aug(at::Tensor store, at::Tensor labels,
@@ -203,6 +206,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("conv2d_dgrad_bn", &conv2d_dgrad_bn);
     m.def("conv2d_wgrad", &conv2d_wgrad);
     m.def("conv2d_wgrad_bias", &conv2d_wgrad_bias);
+    m.def("conv2d_wgrad_plan", &conv2d_wgrad_plan,
+          "(leaf name, split, fused_bias) conv2d_wgrad[_bias] would run for "
+          "this shape under this process's DDPX_WGRAD_V; launches nothing",
+          py::arg("N"), py::arg("C"), py::arg("H"), py::arg("W"),
+          py::arg("Ko"), py::arg("R"), py::arg("S"), py::arg("stride"),
+          py::arg("pad"), py::arg("want_bias"));
     m.def("batch_gather_aug", &batch_gather_aug,
           "uint8 HWC device store -> (bf16 channels_last batch, labels): "
           "gather by index + crop/flip + LUT normalise in one launch",

@@ -14,6 +14,8 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include <climits>
+#include <string>
+#include <tuple>
 #include "common.h"
 
 typedef short bf16x8_t __attribute__((ext_vector_type(8)));
@@ -538,134 +540,14 @@ __global__ void k_conv_small_cin(const bf16* __restrict__ x,
 
 // -------------------------------------------------------- backward weight ---
 
-// slab[s][ko, rsc] = Σ_{m in split s} dy[m][ko] · im2col(x)[m][rsc]
-// 64×64 output tile per block (4 waves, 32×32 each), contraction staged
-// 64-deep through DOUBLE-BUFFERED LDS with register staging (the writes
-// transpose m-major sources to [ko|rsc][m] images, which glds cannot do —
-// cdna_hip_programming.md T10/T14 note).  One barrier per 64-m step: the
-// t+1 tile is gathered into registers while t's MFMAs run, stored to the
-// other buffer, then a single barrier publishes it.
-constexpr int WBM = 64, WBN = 64, WBK = 64;
-constexpr int WLDM = WBK + 8;
-
-__global__ __launch_bounds__(256)
-void k_conv_wgrad(const bf16* __restrict__ dy, const bf16* __restrict__ x,
-                  float* __restrict__ slab, ConvShape cs, long M, int Kgemm,
-                  int S) {
-    __shared__ bf16 lds_a[2][WBM][WLDM];   // [buf][ko][m]
-    __shared__ bf16 lds_b[2][WBN][WLDM];   // [buf][rsc][m]
-    const int ko0 = blockIdx.x * WBM;
-    const int rc0 = blockIdx.y * WBN;
-    const int split = blockIdx.z;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wid = tid >> 6, wr = wid >> 1, wc = wid & 1;
-
-    f32x4 acc[2][2] = {};
-    // staging assignment: thread -> (mloc = tid%64, half j-rows j8 and j8+32)
-    const int mloc = tid & 63;
-    const int jbase = (tid >> 6) * 8;
-
-    const long mstep = (long)S * WBK;
-    const long m_begin = (long)split * WBK;
-
-    bf16x8_t va[2], vb[2];
-    auto gather = [&](long mt) {
-        long gm = mt + mloc;
-        #pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            int j8 = jbase + half * 32;
-            va[half] = bf16x8_t{};
-            vb[half] = bf16x8_t{};
-            if (gm < M) {
-                if (ko0 + j8 < cs.Ko)
-                    va[half] = *reinterpret_cast<const bf16x8_t*>(
-                        &dy[gm * cs.Ko + ko0 + j8]);
-                int gk = rc0 + j8;
-                if (gk < Kgemm) {
-                    unsigned rem = fd_div((unsigned)gm, cs.fdQ);
-                    int q = fd_mod((unsigned)gm, cs.fdQ, rem);
-                    unsigned n = fd_div(rem, cs.fdP);
-                    int p = fd_mod(rem, cs.fdP, n);
-                    unsigned rs = fd_div(gk, cs.fdC);
-                    int c = fd_mod(gk, cs.fdC, rs);
-                    int r = fd_div(rs, cs.fdS);
-                    int s = fd_mod(rs, cs.fdS, r);
-                    int h = p * cs.stride + r - cs.pad;
-                    int wcol = q * cs.stride + s - cs.pad;
-                    if (h >= 0 && h < cs.H && wcol >= 0 && wcol < cs.W)
-                        vb[half] = *reinterpret_cast<const bf16x8_t*>(
-                            &x[(((long)n * cs.H + h) * cs.W + wcol) * cs.C + c]);
-                }
-            }
-        }
-    };
-    auto store = [&](int buf) {
-        #pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            int j8 = jbase + half * 32;
-            #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                lds_a[buf][j8 + j][mloc] = ((bf16*)&va[half])[j];
-                lds_b[buf][j8 + j][mloc] = ((bf16*)&vb[half])[j];
-            }
-        }
-    };
-    auto compute = [&](int buf) {
-        #pragma unroll
-        for (int ks = 0; ks < WBK; ks += 32) {
-            bf16x8_t af[2], bfr[2];
-            const int kcol = ks + (lane >> 4) * 8;
-            #pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-                af[mi] = *reinterpret_cast<const bf16x8_t*>(
-                    &lds_a[buf][wr * 32 + mi * 16 + (lane & 15)][kcol]);
-            #pragma unroll
-            for (int ni = 0; ni < 2; ++ni)
-                bfr[ni] = *reinterpret_cast<const bf16x8_t*>(
-                    &lds_b[buf][wc * 32 + ni * 16 + (lane & 15)][kcol]);
-            #pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-                #pragma unroll
-                for (int ni = 0; ni < 2; ++ni)
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                        af[mi], bfr[ni], acc[mi][ni], 0, 0, 0);
-        }
-    };
-
-    if (m_begin < M) {
-        gather(m_begin);
-        store(0);
-        __syncthreads();
-        int buf = 0;
-        for (long mt = m_begin;;) {
-            long mt_next = mt + mstep;
-            bool more = mt_next < M;
-            if (more) gather(mt_next);
-            compute(buf);
-            if (!more) break;
-            store(buf ^ 1);
-            __syncthreads();
-            buf ^= 1;
-            mt = mt_next;
-        }
-    }
-
-    #pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-        #pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-            int col = rc0 + wc * 32 + ni * 16 + (lane & 15);
-            if (col >= Kgemm) continue;
-            #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                int row = ko0 + wr * 32 + mi * 16 + (lane >> 4) * 4 + r;
-                if (row >= cs.Ko) continue;
-                slab[((long)split * cs.Ko + row) * Kgemm + col] =
-                    acc[mi][ni][r];
-            }
-        }
-}
+// Every MFMA leaf writes slab[s][ko, rsc] = Σ_{m in split s} dy[m][ko] ·
+// im2col(x)[m][rsc] on a (ko tiles, rsc tiles, S) grid; split s owns the
+// contraction steps s, s + S, ... of the leaf's DEPTH.  The operands are
+// m-major in memory and the MFMA wants m contiguous per lane, so the leaves
+// differ in how they transpose: packed pair stores (sb_pair, wide_pair) or
+// LDS-DMA plus transposed reads (wide_dma).  plan_wgrad (hosts, below) picks
+// the leaf and S.
+constexpr int WBM = 64, WBN = 64;   // sb_pair tile; the wide leaves use 128
 
 // combine slab -> dw fp32 in torch KCRS layout (fixed order, deterministic).
 // BIAS: the slab carries S x Ko bias partials behind the S dw slices (see
@@ -734,201 +616,6 @@ __global__ void k_wgrad_combine_stage(const float* __restrict__ slab, int S,
     }
     if (s < ce) v0 += slab[(long)s * ld + i];
     slab2[(long)blockIdx.y * ld + i] = v0 + v1;
-}
-
-// Single-buffer 32-deep wgrad variant (the pre-pipelining shape; kept for
-// A/B selection via DDPX_WGRAD_V=sb — the profiler decides, not intuition).
-constexpr int SBK = 32;
-constexpr int SLDK = SBK + 8;
-
-__global__ __launch_bounds__(256)
-void k_conv_wgrad_sb(const bf16* __restrict__ dy, const bf16* __restrict__ x,
-                     float* __restrict__ slab, ConvShape cs, long M, int Kgemm,
-                     int S) {
-    __shared__ bf16 lds_a[WBM][SLDK];   // [ko][m]
-    __shared__ bf16 lds_b[WBN][SLDK];   // [rsc][m]
-    const int ko0 = blockIdx.x * WBM;
-    const int rc0 = blockIdx.y * WBN;
-    const int split = blockIdx.z;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wid = tid >> 6, wr = wid >> 1, wc = wid & 1;
-
-    f32x4 acc[2][2] = {};
-    const int mloc = tid & 31;
-    const int j8 = (tid >> 5) * 8;
-
-    const long m_begin = (long)split * SBK;
-    for (long mt = m_begin; mt < M; mt += (long)S * SBK) {
-        long gm = mt + mloc;
-        bf16x8_t va = {};
-        if (gm < M && ko0 + j8 < cs.Ko)
-            va = *reinterpret_cast<const bf16x8_t*>(
-                &dy[gm * cs.Ko + ko0 + j8]);
-        #pragma unroll
-        for (int j = 0; j < 8; ++j) lds_a[j8 + j][mloc] = ((bf16*)&va)[j];
-        bf16x8_t vb = {};
-        int gk = rc0 + j8;
-        if (gm < M && gk < Kgemm) {
-            unsigned rem = fd_div((unsigned)gm, cs.fdQ);
-            int q = fd_mod((unsigned)gm, cs.fdQ, rem);
-            unsigned n = fd_div(rem, cs.fdP);
-            int p = fd_mod(rem, cs.fdP, n);
-            unsigned rs = fd_div(gk, cs.fdC);
-            int c = fd_mod(gk, cs.fdC, rs);
-            int r = fd_div(rs, cs.fdS);
-            int s = fd_mod(rs, cs.fdS, r);
-            int h = p * cs.stride + r - cs.pad;
-            int wcol = q * cs.stride + s - cs.pad;
-            if (h >= 0 && h < cs.H && wcol >= 0 && wcol < cs.W)
-                vb = *reinterpret_cast<const bf16x8_t*>(
-                    &x[(((long)n * cs.H + h) * cs.W + wcol) * cs.C + c]);
-        }
-        #pragma unroll
-        for (int j = 0; j < 8; ++j) lds_b[j8 + j][mloc] = ((bf16*)&vb)[j];
-        __syncthreads();
-
-        bf16x8_t af[2], bfr[2];
-        const int kcol = (lane >> 4) * 8;
-        #pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-            af[mi] = *reinterpret_cast<const bf16x8_t*>(
-                &lds_a[wr * 32 + mi * 16 + (lane & 15)][kcol]);
-        #pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-            bfr[ni] = *reinterpret_cast<const bf16x8_t*>(
-                &lds_b[wc * 32 + ni * 16 + (lane & 15)][kcol]);
-        #pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-            #pragma unroll
-            for (int ni = 0; ni < 2; ++ni)
-                acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                    af[mi], bfr[ni], acc[mi][ni], 0, 0, 0);
-        __syncthreads();
-    }
-
-    #pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-        #pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-            int col = rc0 + wc * 32 + ni * 16 + (lane & 15);
-            if (col >= Kgemm) continue;
-            #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                int row = ko0 + wr * 32 + mi * 16 + (lane >> 4) * 4 + r;
-                if (row >= cs.Ko) continue;
-                slab[((long)split * cs.Ko + row) * Kgemm + col] =
-                    acc[mi][ni][r];
-            }
-        }
-}
-
-// Wide wgrad variant: 128(ko) x 128(rsc) tile, DEPTH-deep contraction —
-// more MFMA work per barrier pair than the 64x64 tile at the same
-// per-thread staging cost per element (transposed bf16x8 stores).
-// Requires Ko >= 128 and Kgemm >= 128 (host falls back to sb otherwise).
-template <int DEPTH>
-__global__ __launch_bounds__(256)
-void k_conv_wgrad_wide(const bf16* __restrict__ dy, const bf16* __restrict__ x,
-                       float* __restrict__ slab, ConvShape cs, long M,
-                       int Kgemm, int S) {
-    __shared__ bf16 lds_a[128][DEPTH + 8];   // [ko][m]
-    __shared__ bf16 lds_b[128][DEPTH + 8];   // [rsc][m]
-    const int ko0 = blockIdx.x * 128;
-    const int rc0 = blockIdx.y * 128;
-    const int split = blockIdx.z;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wid = tid >> 6, wr = wid >> 1, wc = wid & 1;
-
-    f32x4 acc[4][4] = {};
-    const int mloc = tid % DEPTH;
-    const int jb = (tid / DEPTH) * 8;
-    constexpr int JSTEP = (256 / DEPTH) * 8;
-
-    const long m_begin = (long)split * DEPTH;
-    for (long mt = m_begin; mt < M; mt += (long)S * DEPTH) {
-        long gm = mt + mloc;
-        const bool valid = gm < M;
-        #pragma unroll
-        for (int j = jb; j < 128; j += JSTEP) {
-            bf16x8_t va = {};
-            if (valid && ko0 + j < cs.Ko)
-                va = *reinterpret_cast<const bf16x8_t*>(
-                    &dy[gm * cs.Ko + ko0 + j]);
-            #pragma unroll
-            for (int jj = 0; jj < 8; ++jj)
-                lds_a[j + jj][mloc] = ((bf16*)&va)[jj];
-        }
-        if (valid) {
-            unsigned rem = fd_div((unsigned)gm, cs.fdQ);
-            int q = fd_mod((unsigned)gm, cs.fdQ, rem);
-            unsigned n = fd_div(rem, cs.fdP);
-            int p = fd_mod(rem, cs.fdP, n);
-            #pragma unroll
-            for (int j = jb; j < 128; j += JSTEP) {
-                bf16x8_t vb = {};
-                int gk = rc0 + j;
-                if (gk < Kgemm) {
-                    unsigned rs = fd_div(gk, cs.fdC);
-                    int c = fd_mod(gk, cs.fdC, rs);
-                    int r = fd_div(rs, cs.fdS);
-                    int s = fd_mod(rs, cs.fdS, r);
-                    int h = p * cs.stride + r - cs.pad;
-                    int wcol = q * cs.stride + s - cs.pad;
-                    if (h >= 0 && h < cs.H && wcol >= 0 && wcol < cs.W)
-                        vb = *reinterpret_cast<const bf16x8_t*>(
-                            &x[(((long)n * cs.H + h) * cs.W + wcol) * cs.C + c]);
-                }
-                #pragma unroll
-                for (int jj = 0; jj < 8; ++jj)
-                    lds_b[j + jj][mloc] = ((bf16*)&vb)[jj];
-            }
-        } else {
-            #pragma unroll
-            for (int j = jb; j < 128; j += JSTEP)
-                #pragma unroll
-                for (int jj = 0; jj < 8; ++jj)
-                    lds_b[j + jj][mloc] = (bf16)0;
-        }
-        __syncthreads();
-
-        #pragma unroll
-        for (int ks = 0; ks < DEPTH; ks += 32) {
-            bf16x8_t af[4], bfr[4];
-            const int kcol = ks + (lane >> 4) * 8;
-            #pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-                af[mi] = *reinterpret_cast<const bf16x8_t*>(
-                    &lds_a[wr * 64 + mi * 16 + (lane & 15)][kcol]);
-            #pragma unroll
-            for (int ni = 0; ni < 4; ++ni)
-                bfr[ni] = *reinterpret_cast<const bf16x8_t*>(
-                    &lds_b[wc * 64 + ni * 16 + (lane & 15)][kcol]);
-            #pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-                #pragma unroll
-                for (int ni = 0; ni < 4; ++ni)
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                        af[mi], bfr[ni], acc[mi][ni], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-
-    #pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-        #pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-            int col = rc0 + wc * 64 + ni * 16 + (lane & 15);
-            if (col >= Kgemm) continue;
-            #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                int row = ko0 + wr * 64 + mi * 16 + (lane >> 4) * 4 + r;
-                if (row >= cs.Ko) continue;
-                slab[((long)split * cs.Ko + row) * Kgemm + col] =
-                    acc[mi][ni][r];
-            }
-        }
 }
 
 // Pair-m single-buffer 64x64 wgrad: thread halves split the two operands;
@@ -1066,9 +753,12 @@ void k_conv_wgrad_sb_pair(const bf16* __restrict__ dy,
         }
 }
 
-// Pair-m wide wgrad: each thread stages TWO consecutive m's per j-group so
-// LDS writes are packed b32 (16 stores/operand/iter vs 32 conflicted b16) —
-// the stage phase of the wide kernel is store-issue bound.
+// Pair-m wide wgrad: 128(ko) x 128(rsc) tile, DEPTH-deep contraction (needs
+// Ko >= 128 and Kgemm >= 128).  Each thread stages TWO consecutive m's per
+// j-group so LDS writes are packed b32 (16 stores/operand/iter vs 32
+// conflicted b16) — the stage phase of this tile is store-issue bound.
+// wide_dma replaced it in the automatic dispatch; it stays as that leaf's
+// bit-identity oracle (DDPX_WGRAD_V=wp / wq).
 //
 // BIAS: the blockIdx.y == 0 blocks (one per (ko tile, split)) also sum the
 // staged dy tile along m straight from lds_a — two threads per ko row, one
@@ -1748,10 +1438,10 @@ __global__ void k_wgrad_small_combine(const float* __restrict__ slab, int S,
 
 // ------------------------------------------------------------------ hosts ---
 
-static ConvShape make_shape(const at::Tensor& x, int Ko, int R, int S,
+static ConvShape make_shape(int N, int C, int H, int W, int Ko, int R, int S,
                             int stride, int pad) {
     ConvShape cs;
-    cs.N = x.size(0); cs.C = x.size(1); cs.H = x.size(2); cs.W = x.size(3);
+    cs.N = N; cs.C = C; cs.H = H; cs.W = W;
     cs.Ko = Ko; cs.R = R; cs.S = S; cs.stride = stride; cs.pad = pad;
     cs.P = (cs.H + 2 * pad - R) / stride + 1;
     cs.Q = (cs.W + 2 * pad - S) / stride + 1;
@@ -1759,12 +1449,68 @@ static ConvShape make_shape(const at::Tensor& x, int Ko, int R, int S,
     return cs;
 }
 
-std::vector<at::Tensor> conv2d_fwd_stats(at::Tensor x, at::Tensor w,
-                                         c10::optional<at::Tensor> bias,
-                                         long stride, long pad);
+static ConvShape make_shape(const at::Tensor& x, int Ko, int R, int S,
+                            int stride, int pad) {
+    return make_shape(x.size(0), x.size(1), x.size(2), x.size(3), Ko, R, S,
+                      stride, pad);
+}
 
-at::Tensor conv2d_fwd(at::Tensor x, at::Tensor w,
-                      c10::optional<at::Tensor> bias, long stride, long pad) {
+static at::Tensor empty_nhwc(const at::Tensor& like, long n, long c, long h,
+                             long w) {
+    return at::empty({n, c, h, w},
+                     like.options().memory_format(at::MemoryFormat::ChannelsLast));
+}
+
+// The one tile choice of forward and dgrad: a 128-channel output tile on
+// 2x2 waves from 128 output channels up, else (or with narrow) 64 channels
+// on 4x1 waves.
+// NOTE: a 256-row tile for the narrow (< 128 channels) case was tried and
+// REVERTED — its 40 KB LDS drops residency 6 -> 4 blocks/CU and measured
+// 20-45% slower (same lesson as the 2-buf glds ring: this kernel lives on
+// block-level parallelism).
+template <int MODE, bool STRIDE1 = true>
+static void launch_conv_gemm(hipStream_t stream, int grid_m, int n_channels,
+                             bool narrow, const bf16* Asrc, const bf16* Bsrc,
+                             const float* bias, bf16* out,
+                             const ConvShape& cs, long M, int Kgemm,
+                             float* stats, BnFuse bn, const bf16* addin) {
+    if (n_channels >= 128 && !narrow)
+        hipLaunchKernelGGL((k_conv_gemm<MODE, 128, 2, 2, STRIDE1>),
+                           dim3(grid_m, ceil_div_i(n_channels, 128)),
+                           dim3(256), 0, stream, Asrc, Bsrc, bias, out, cs,
+                           (int)M, Kgemm, n_channels, stats, bn, addin);
+    else
+        hipLaunchKernelGGL((k_conv_gemm<MODE, 64, 4, 1, STRIDE1>),
+                           dim3(grid_m, ceil_div_i(n_channels, 64)),
+                           dim3(256), 0, stream, Asrc, Bsrc, bias, out, cs,
+                           (int)M, Kgemm, n_channels, stats, bn, addin);
+    HIP_CHECK_LAST();
+}
+
+static void launch_conv_gemm_cls(hipStream_t stream, int grid_m,
+                                 int n_channels, int ncls, const bf16* Asrc,
+                                 const bf16* Bsrc, bf16* out,
+                                 const ClsPack& pack) {
+    if (n_channels >= 128)
+        hipLaunchKernelGGL((k_conv_gemm_cls<128, 2, 2>),
+                           dim3(grid_m, ceil_div_i(n_channels, 128), ncls),
+                           dim3(256), 0, stream, Asrc, Bsrc, out, pack,
+                           n_channels);
+    else
+        hipLaunchKernelGGL((k_conv_gemm_cls<64, 4, 1>),
+                           dim3(grid_m, ceil_div_i(n_channels, 64), ncls),
+                           dim3(256), 0, stream, Asrc, Bsrc, out, pack,
+                           n_channels);
+    HIP_CHECK_LAST();
+}
+
+// y, and with want_stats the per-channel partial sum / sumsq slab
+// [2][Ko][gridM] for the consuming BN (SURVEY §7 "fuse normalisation work
+// into the producing kernel"), which needs the MFMA conv.
+static std::vector<at::Tensor> conv_fwd_impl(
+        const at::Tensor& x, const at::Tensor& w,
+        const c10::optional<at::Tensor>& bias, long stride, long pad,
+        bool want_stats) {
     // x: NCHW logical / channels_last physical bf16; w: KCRS logical /
     // channels_last physical (= KRSC memory) bf16
     TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16);
@@ -1772,52 +1518,55 @@ at::Tensor conv2d_fwd(at::Tensor x, at::Tensor w,
                               (int)stride, (int)pad);
     int Kgemm = cs.R * cs.S * cs.C;
     long M = (long)cs.N * cs.P * cs.Q;
-    auto y = at::empty({cs.N, cs.Ko, cs.P, cs.Q},
-                       x.options().memory_format(at::MemoryFormat::ChannelsLast));
     auto stream = at::hip::getCurrentHIPStream();
     const float* bp = bias.has_value() ? bias->data_ptr<float>() : nullptr;
     const bf16* xp = reinterpret_cast<const bf16*>(x.data_ptr());
     const bf16* wp = reinterpret_cast<const bf16*>(w.data_ptr());
+    auto y = empty_nhwc(x, cs.N, cs.Ko, cs.P, cs.Q);
     bf16* yp = reinterpret_cast<bf16*>(y.data_ptr());
 
-    if (cs.C < 8) {
+    if (cs.C < 8 && !want_stats) {
         TORCH_CHECK(cs.Ko % 8 == 0);
         int lds = cs.Ko * Kgemm * 2;
         long total = M * (cs.Ko / 8);
         int blocks = std::min<long>(8192, ceil_div_i(total, 256));
         hipLaunchKernelGGL(k_conv_small_cin, dim3(blocks), dim3(256), lds,
                            stream.stream(), xp, wp, bp, yp, cs, M);
-    } else {
-        TORCH_CHECK(cs.C % 8 == 0, "conv fwd needs C % 8 == 0");
-        // the staged epilogue stores 16 B (8-channel) chunks per row
-        TORCH_CHECK(cs.Ko % 8 == 0, "conv fwd needs Ko % 8 == 0");
-        static const char* tbn_env = getenv("DDPX_CONV_TBN64");
-        if (cs.Ko >= 128 && !tbn_env) {
-            dim3 grid(ceil_div_i(M, CBM), ceil_div_i(cs.Ko, 128));
-            hipLaunchKernelGGL((k_conv_gemm<0, 128, 2, 2>), grid, dim3(256), 0,
-                               stream.stream(), xp, wp, bp, yp, cs, (int)M,
-                               Kgemm, cs.Ko);
-        } else {
-            // NOTE: a 256-row tile for the narrow (Ko<128) case was tried
-            // and REVERTED — its 40 KB LDS drops residency 6 -> 4 blocks/CU
-            // and measured 20-45% slower (same lesson as the 2-buf glds
-            // ring: this kernel lives on block-level parallelism).
-            dim3 grid(ceil_div_i(M, CBM), ceil_div_i(cs.Ko, 64));
-            hipLaunchKernelGGL((k_conv_gemm<0, 64, 4, 1>), grid, dim3(256), 0,
-                               stream.stream(), xp, wp, bp, yp, cs, (int)M,
-                               Kgemm, cs.Ko);
-        }
+        HIP_CHECK_LAST();
+        return {y, at::Tensor()};
     }
-    HIP_CHECK_LAST();
-    return y;
+    TORCH_CHECK(cs.C % 8 == 0, want_stats
+                ? "stats path needs the MFMA conv (C%8==0)"
+                : "conv fwd needs C % 8 == 0");
+    // the staged epilogue stores 16 B (8-channel) chunks per row
+    TORCH_CHECK(cs.Ko % 8 == 0, "conv fwd needs Ko % 8 == 0");
+    const int gridM = ceil_div_i(M, CBM);
+    at::Tensor slab;
+    if (want_stats)
+        slab = at::empty({2, (long)cs.Ko, (long)gridM},
+                         x.options().dtype(at::kFloat));
+    static const char* tbn_env = getenv("DDPX_CONV_TBN64");
+    launch_conv_gemm<0>(stream.stream(), gridM, cs.Ko,
+                        tbn_env && !want_stats, xp, wp, bp, yp, cs, M, Kgemm,
+                        want_stats ? slab.data_ptr<float>() : nullptr,
+                        BnFuse{}, nullptr);
+    return {y, slab};
 }
 
-at::Tensor conv2d_dgrad(at::Tensor dy, at::Tensor wt2, long N, long C,
-                        long H, long W, long R, long S, long stride, long pad,
-                        c10::optional<at::Tensor> addend) {
-    // dy: NCHW logical / channels_last bf16 [N,Ko,P,Q]; wt2: [C, R*S*Ko] bf16
-    // addend: optional bf16 channels_last [N,C,H,W] streamed into the
-    // epilogue (dx += addend — the fused ResNet skip-grad; stride 1 only)
+at::Tensor conv2d_fwd(at::Tensor x, at::Tensor w,
+                      c10::optional<at::Tensor> bias, long stride, long pad) {
+    return conv_fwd_impl(x, w, bias, stride, pad, false)[0];
+}
+
+std::vector<at::Tensor> conv2d_fwd_stats(at::Tensor x, at::Tensor w,
+                                         c10::optional<at::Tensor> bias,
+                                         long stride, long pad) {
+    return conv_fwd_impl(x, w, bias, stride, pad, true);
+}
+
+// dy: NCHW logical / channels_last bf16 [N,Ko,P,Q]; wt2: [C, R*S*Ko] bf16
+static ConvShape dgrad_shape(const at::Tensor& dy, long N, long C, long H,
+                             long W, long R, long S, long stride, long pad) {
     ConvShape cs;
     cs.N = N; cs.C = C; cs.H = H; cs.W = W;
     cs.Ko = dy.size(1); cs.P = dy.size(2); cs.Q = dy.size(3);
@@ -1826,42 +1575,50 @@ at::Tensor conv2d_dgrad(at::Tensor dy, at::Tensor wt2, long N, long C,
     TORCH_CHECK(cs.Ko % 8 == 0, "conv dgrad needs Ko % 8 == 0");
     // the staged epilogue stores 16 B (8-channel) chunks per dx row
     TORCH_CHECK(cs.C % 8 == 0, "conv dgrad needs C % 8 == 0");
-    int Kgemm = cs.R * cs.S * cs.Ko;
-    long M = (long)cs.N * cs.H * cs.W;
-    auto dx = at::empty({(long)cs.N, (long)cs.C, (long)cs.H, (long)cs.W},
-                        dy.options().memory_format(at::MemoryFormat::ChannelsLast));
-    auto stream = at::hip::getCurrentHIPStream();
-    // NOTE: zero-stuffing dy to reach the stride-1 gather was tried and
-    // REVERTED — measured slower at ResNet's strided shapes (r18 3x3/2:
-    // 113 vs 99 us, 1x1/2: 44 vs 22 us): the 4x stuffed-dy traffic costs
-    // more than the divisibility-checked gather saves.
-    const bf16* dyp_ = reinterpret_cast<const bf16*>(dy.data_ptr());
-    const bf16* wt2p = reinterpret_cast<const bf16*>(wt2.data_ptr());
-    bf16* dxp = reinterpret_cast<bf16*>(dx.data_ptr());
+    return cs;
+}
+
+// Stride-1 dgrad.  addend: optional bf16 channels_last [N,C,H,W] streamed
+// into the epilogue (dx += addend — the fused ResNet skip-grad).  bn: with
+// bn.slab set the epilogue also emits the upstream BN's backward partials.
+static at::Tensor dgrad_stride1(const at::Tensor& dy, const at::Tensor& wt2,
+                                const ConvShape& cs,
+                                const c10::optional<at::Tensor>& addend,
+                                BnFuse bn) {
+    auto dx = empty_nhwc(dy, cs.N, cs.C, cs.H, cs.W);
     const bf16* adp = nullptr;
     if (addend.has_value()) {
-        TORCH_CHECK(cs.stride == 1, "fused dgrad addend needs stride 1");
         TORCH_CHECK(addend->sizes() == dx.sizes() &&
                     addend->scalar_type() == at::kBFloat16);
         adp = reinterpret_cast<const bf16*>(addend->data_ptr());
     }
-    if (cs.stride == 1) {
-        if (cs.C >= 128) {
-            dim3 grid(ceil_div_i(M, CBM), ceil_div_i(cs.C, 128));
-            hipLaunchKernelGGL((k_conv_gemm<1, 128, 2, 2, true>), grid,
-                               dim3(256), 0, stream.stream(), dyp_, wt2p,
-                               nullptr, dxp, cs, (int)M, Kgemm, cs.C,
-                               nullptr, BnFuse{}, adp);
-        } else {
-            dim3 grid(ceil_div_i(M, CBM), ceil_div_i(cs.C, 64));
-            hipLaunchKernelGGL((k_conv_gemm<1, 64, 4, 1, true>), grid,
-                               dim3(256), 0, stream.stream(), dyp_, wt2p,
-                               nullptr, dxp, cs, (int)M, Kgemm, cs.C,
-                               nullptr, BnFuse{}, adp);
-        }
-        HIP_CHECK_LAST();
-        return dx;
-    }
+    const long M = (long)cs.N * cs.H * cs.W;
+    launch_conv_gemm<1>(at::hip::getCurrentHIPStream().stream(),
+                        ceil_div_i(M, CBM), cs.C, false,
+                        reinterpret_cast<const bf16*>(dy.data_ptr()),
+                        reinterpret_cast<const bf16*>(wt2.data_ptr()),
+                        nullptr, reinterpret_cast<bf16*>(dx.data_ptr()), cs,
+                        M, cs.R * cs.S * cs.Ko, nullptr, bn, adp);
+    return dx;
+}
+
+at::Tensor conv2d_dgrad(at::Tensor dy, at::Tensor wt2, long N, long C,
+                        long H, long W, long R, long S, long stride, long pad,
+                        c10::optional<at::Tensor> addend) {
+    ConvShape cs = dgrad_shape(dy, N, C, H, W, R, S, stride, pad);
+    TORCH_CHECK(!addend.has_value() || cs.stride == 1,
+                "fused dgrad addend needs stride 1");
+    if (cs.stride == 1) return dgrad_stride1(dy, wt2, cs, addend, BnFuse{});
+
+    // NOTE: zero-stuffing dy to reach the stride-1 gather was tried and
+    // REVERTED — measured slower at ResNet's strided shapes (r18 3x3/2:
+    // 113 vs 99 us, 1x1/2: 44 vs 22 us): the 4x stuffed-dy traffic costs
+    // more than the divisibility-checked gather saves.
+    auto dx = empty_nhwc(dy, cs.N, cs.C, cs.H, cs.W);
+    auto stream = at::hip::getCurrentHIPStream();
+    const bf16* dyp_ = reinterpret_cast<const bf16*>(dy.data_ptr());
+    const bf16* wt2p = reinterpret_cast<const bf16*>(wt2.data_ptr());
+    bf16* dxp = reinterpret_cast<bf16*>(dx.data_ptr());
     // stride > 1: sub-grid class decomposition — one MODE-2 launch per
     // (a, b) residue class, each summing ONLY its contributing taps
     // (the divisibility-checked single launch wastes stride^2 x MFMA work
@@ -1928,37 +1685,15 @@ at::Tensor conv2d_dgrad(at::Tensor dy, at::Tensor wt2, long N, long C,
                 ++ncls;
             } else {
                 // >4 contributing classes (stride > 2): per-class launch
-                if (cs.C >= 128) {
-                    dim3 grid(ceil_div_i(M2, CBM), ceil_div_i(cs.C, 128));
-                    hipLaunchKernelGGL((k_conv_gemm<2, 128, 2, 2, true>),
-                                       grid, dim3(256), 0, stream.stream(),
-                                       dyp_, wt2p, nullptr, dxp, c2, (int)M2,
-                                       K2, cs.C);
-                } else {
-                    dim3 grid(ceil_div_i(M2, CBM), ceil_div_i(cs.C, 64));
-                    hipLaunchKernelGGL((k_conv_gemm<2, 64, 4, 1, true>),
-                                       grid, dim3(256), 0, stream.stream(),
-                                       dyp_, wt2p, nullptr, dxp, c2, (int)M2,
-                                       K2, cs.C);
-                }
-                HIP_CHECK_LAST();
+                launch_conv_gemm<2>(stream.stream(), ceil_div_i(M2, CBM),
+                                    cs.C, false, dyp_, wt2p, nullptr, dxp,
+                                    c2, M2, K2, nullptr, BnFuse{}, nullptr);
             }
         }
     }
-    if (ncls > 0) {
-        if (cs.C >= 128) {
-            dim3 grid(maxTiles, ceil_div_i(cs.C, 128), ncls);
-            hipLaunchKernelGGL((k_conv_gemm_cls<128, 2, 2>), grid, dim3(256),
-                               0, stream.stream(), dyp_, wt2p, dxp, pack,
-                               (int)cs.C);
-        } else {
-            dim3 grid(maxTiles, ceil_div_i(cs.C, 64), ncls);
-            hipLaunchKernelGGL((k_conv_gemm_cls<64, 4, 1>), grid, dim3(256),
-                               0, stream.stream(), dyp_, wt2p, dxp, pack,
-                               (int)cs.C);
-        }
-        HIP_CHECK_LAST();
-    }
+    if (ncls > 0)
+        launch_conv_gemm_cls(stream.stream(), maxTiles, cs.C, ncls, dyp_,
+                             wt2p, dxp, pack);
     return dx;
 }
 
@@ -1971,18 +1706,8 @@ std::vector<at::Tensor> conv2d_dgrad_bn(at::Tensor dy, at::Tensor wt2,
     // stride-1 dgrad that ALSO emits the upstream BN's backward partial
     // sums ([2][C][gridM], fed to bn_bwd's pre_slab) — the BN partial pass
     // never re-reads x/dy.
-    ConvShape cs;
-    cs.N = N; cs.C = C; cs.H = H; cs.W = W;
-    cs.Ko = dy.size(1); cs.P = dy.size(2); cs.Q = dy.size(3);
-    cs.R = R; cs.S = S; cs.stride = 1; cs.pad = pad;
-    init_fastdiv(cs);
-    TORCH_CHECK(cs.Ko % 8 == 0 && cs.C % 8 == 0);
-    int Kgemm = cs.R * cs.S * cs.Ko;
-    long M = (long)cs.N * cs.H * cs.W;
-    auto dx = at::empty({(long)cs.N, (long)cs.C, (long)cs.H, (long)cs.W},
-                        dy.options().memory_format(at::MemoryFormat::ChannelsLast));
-    auto stream = at::hip::getCurrentHIPStream();
-    int gridM = ceil_div_i(M, CBM);
+    ConvShape cs = dgrad_shape(dy, N, C, H, W, R, S, 1, pad);
+    const int gridM = ceil_div_i((long)cs.N * cs.H * cs.W, CBM);
     auto slab = at::empty({2, (long)cs.C, (long)gridM},
                           dy.options().dtype(at::kFloat));
     BnFuse bn;
@@ -1992,158 +1717,143 @@ std::vector<at::Tensor> conv2d_dgrad_bn(at::Tensor dy, at::Tensor wt2,
     bn.mean = bn_mean.data_ptr<float>();
     bn.invstd = bn_invstd.data_ptr<float>();
     bn.slab = slab.data_ptr<float>();
-    const bf16* dyp_ = reinterpret_cast<const bf16*>(dy.data_ptr());
-    const bf16* wt2p = reinterpret_cast<const bf16*>(wt2.data_ptr());
-    bf16* dxp = reinterpret_cast<bf16*>(dx.data_ptr());
-    if (cs.C >= 128) {
-        dim3 grid(gridM, ceil_div_i(cs.C, 128));
-        hipLaunchKernelGGL((k_conv_gemm<1, 128, 2, 2, true>), grid,
-                           dim3(256), 0, stream.stream(), dyp_, wt2p,
-                           nullptr, dxp, cs, (int)M, Kgemm, cs.C, nullptr,
-                           bn);
-    } else {
-        dim3 grid(gridM, ceil_div_i(cs.C, 64));
-        hipLaunchKernelGGL((k_conv_gemm<1, 64, 4, 1, true>), grid,
-                           dim3(256), 0, stream.stream(), dyp_, wt2p,
-                           nullptr, dxp, cs, (int)M, Kgemm, cs.C, nullptr,
-                           bn);
-    }
-    HIP_CHECK_LAST();
-    return {dx, slab};
+    return {dgrad_stride1(dy, wt2, cs, c10::nullopt, bn), slab};
 }
 
 at::Tensor col_sum(at::Tensor x);   // gemm.hip
 
-// dw, and with want_bias also db = sum of dy over (n, p, q).  The leaves
-// Toy_Net runs (wide_dma<32>, wide_dma<64>, the streaming stem kernel)
-// produce db inside the wgrad and combine launches; every other leaf takes
-// the separate column-sum pass over dy.
-static std::vector<at::Tensor> wgrad_impl(const at::Tensor& dy,
-                                          const at::Tensor& x, long R,
-                                          long S, long stride, long pad,
-                                          bool want_bias) {
-    ConvShape cs = make_shape(x, dy.size(1), (int)R, (int)S, (int)stride,
-                              (int)pad);
-    TORCH_CHECK(cs.P == dy.size(2) && cs.Q == dy.size(3));
-    long M = (long)cs.N * cs.P * cs.Q;
-    int Kgemm = cs.R * cs.S * cs.C;
-    auto stream = at::hip::getCurrentHIPStream();
-    auto dw = at::empty({(long)cs.Ko, (long)cs.C, (long)cs.R, (long)cs.S},
-                        x.options().dtype(at::kFloat));
-    const bf16* dyp = reinterpret_cast<const bf16*>(dy.data_ptr());
-    const bf16* xp = reinterpret_cast<const bf16*>(x.data_ptr());
-    auto unfused_bias = [&]() -> at::Tensor {
-        if (!want_bias) return at::Tensor();
-        return col_sum(dy.permute({0, 2, 3, 1}).reshape({M, (long)cs.Ko}));
-    };
+// ----------------------------------------------------------- wgrad hosts ---
+
+enum class WgradLeaf {
+    StemStream, C1R3, SmallRsc, SmallCin,       // C < 8: VALU kernels
+    SbPair32, SbPair64,                         // MFMA, 64x64 tile
+    WidePair32, WidePair64, WideDma32, WideDma64,   // MFMA, 128x128 tile
+};
+
+// indexed by WgradLeaf: name, and for the MFMA leaves (one signature, one
+// grid) the kernel without / with the fused bias partials
+using WgradMfmaKernel = void (*)(const bf16*, const bf16*, float*, ConvShape,
+                                 long, int, int);
+static const struct { const char* name; WgradMfmaKernel kern[2]; }
+WGRAD_LEAVES[] = {
+    {"c1_r3_stream", {}}, {"c1_r3", {}}, {"small_rsc", {}}, {"small_cin", {}},
+    {"sb_pair<32>", {k_conv_wgrad_sb_pair<32>, k_conv_wgrad_sb_pair<32>}},
+    {"sb_pair<64>", {k_conv_wgrad_sb_pair<64>, k_conv_wgrad_sb_pair<64>}},
+    {"wide_pair<32>", {k_conv_wgrad_wide_pair<32, false>,
+                       k_conv_wgrad_wide_pair<32, true>}},
+    {"wide_pair<64>", {k_conv_wgrad_wide_pair<64, false>,
+                       k_conv_wgrad_wide_pair<64, true>}},
+    {"wide_dma<32>", {k_conv_wgrad_wide_dma<32, false>,
+                      k_conv_wgrad_wide_dma<32, true>}},
+    {"wide_dma<64>", {k_conv_wgrad_wide_dma<64, false>,
+                      k_conv_wgrad_wide_dma<64, true>}},
+};
+static_assert(sizeof(WGRAD_LEAVES) / sizeof(WGRAD_LEAVES[0]) ==
+              (int)WgradLeaf::WideDma64 + 1, "one row per WgradLeaf");
+
+struct WgradPlan {
+    WgradLeaf leaf;
+    int S;              // split count = slab slices the combine sums
+    int gk, gr;         // MFMA leaves: ko / rsc tile counts, grid (gk, gr, S)
+    bool fused_bias;    // db comes out of the wgrad and combine launches;
+                        // otherwise it is a separate column sum over dy
+};
+
+// DDPX_WGRAD_V, read once per process
+static const char* wgrad_override() {
+    static const char* v = getenv("DDPX_WGRAD_V");
+    return v;
+}
+
+// Which kernel runs for this shape, and how deep it splits: every wgrad
+// dispatch decision is made here and nowhere else.  Pure host arithmetic —
+// no device, no allocation.  The choice is MEASURED (profiles/,
+// tools/bench_kernels.py):
+//   * C < 8 takes a VALU kernel whatever the override says;
+//   * 128x128 wide tile, LDS-DMA staged (wide_dma), 64-deep, for big-Kgemm
+//     convs with enough tiles (with bias: conv3 119 vs 174 us pair-store,
+//     conv4 235 vs 384);
+//   * the same tile 32-DEEP for small-Kgemm or tile-starved-but-deep-M
+//     shapes (conv2 218 vs 282 us pair-store);
+//   * 64x64 pair-store sb_pair otherwise.
+// override (DDPX_WGRAD_V) forces an MFMA leaf for A/B runs: wt = wide_dma at
+// the automatic depth, wt3 = wide_dma<32>, wp = wide_pair<64>, wq =
+// wide_pair<32> (the pair-store leaves wide_dma replaced, profiles/
+// toynet_b1024_1gpu_kernel_stats_wgraddma.md), s / sb = sb_pair<32>, s6 =
+// sb_pair<64>.  A wide leaf forced on a shape the 128x128 tile does not fit
+// runs sb_pair<32>.  Any other value is an error.
+static WgradPlan plan_wgrad(const ConvShape& cs, long M, bool want_bias,
+                            const char* override) {
+    enum { Auto, Dma, Dma32, Pair64, Pair32, Sb32, Sb64 } force = Auto;
+    if (override && override[0]) {
+        const std::string v(override);
+        if (v == "wt") force = Dma;
+        else if (v == "wt3") force = Dma32;
+        else if (v == "wp") force = Pair64;
+        else if (v == "wq") force = Pair32;
+        else if (v == "s" || v == "sb") force = Sb32;
+        else if (v == "s6") force = Sb64;
+        else TORCH_CHECK(false, "DDPX_WGRAD_V=", v, " selects no wgrad "
+                         "kernel; accepted values: wt, wt3, wp, wq, s, sb, "
+                         "s6 (unset or empty: automatic)");
+    }
+    const int Kgemm = cs.R * cs.S * cs.C;
+    WgradPlan p{};
 
     if (cs.C < 8) {
-        int rsc_total = Kgemm;
-        if (cs.C == 1 && cs.R == 3 && cs.S == 3 && cs.Ko % 8 == 0 &&
-            cs.Ko <= 64 && M < INT_MAX) {
+        const bool c1r3 = cs.C == 1 && cs.R == 3 && cs.S == 3;
+        if (c1r3 && cs.Ko % 8 == 0 && cs.Ko <= 64 && M < INT_MAX) {
             // work is dealt in wave loads (rpl rows); a block wants >= 2
             // trips per wave, and 768 blocks = 3 per CU (the occupancy the
             // kernel's registers allow) all stream at once
             const int rpl = 64 / (cs.Ko / 8);
             const long nloads = (M + rpl - 1) / rpl;
-            const int S_ = (int)std::max<long>(
+            p.leaf = WgradLeaf::StemStream;
+            p.S = (int)std::max<long>(
                 1, std::min<long>(768, (nloads + 8 * SU - 1) / (8 * SU)));
-            const long chunk = (nloads + 4L * S_ - 1) / (4L * S_) * rpl;
-            const int nt = want_bias ? 10 : 9;
-            auto slab = at::empty({nt * cs.Ko, S_},
-                                  x.options().dtype(at::kFloat));
-            at::Tensor db;
-            if (want_bias)
-                db = at::empty({(long)cs.Ko}, x.options().dtype(at::kFloat));
-            auto launch = [&](auto kern) {
-                hipLaunchKernelGGL(kern, dim3(S_), dim3(256), 0,
-                                   stream.stream(), dyp, xp,
-                                   slab.data_ptr<float>(), cs, M, chunk);
-            };
-            if (want_bias && cs.pad)
-                launch(k_wgrad_c1_r3_stream<true, true>);
-            else if (want_bias)
-                launch(k_wgrad_c1_r3_stream<true, false>);
-            else if (cs.pad)
-                launch(k_wgrad_c1_r3_stream<false, true>);
-            else
-                launch(k_wgrad_c1_r3_stream<false, false>);
-            HIP_CHECK_LAST();
-            hipLaunchKernelGGL(k_wgrad_small_rsc_combine,
-                               dim3(ceil_div_i(nt * cs.Ko, 4)), dim3(256), 0,
-                               stream.stream(), slab.data_ptr<float>(), S_,
-                               cs, 9, dw.data_ptr<float>(),
-                               want_bias ? db.data_ptr<float>() : nullptr);
-            HIP_CHECK_LAST();
-            return {dw, db};
-        }
-        if (rsc_total <= 16 && cs.Ko <= 64) {
+            p.fused_bias = want_bias;
+        } else if (Kgemm <= 16 && cs.Ko <= 64) {
             // S=8192 measured slower (164 vs 132 us): per-block reduction
             // fixed costs dominate below ~80 rows/walker
-            int S_ = (int)std::max<long>(1, std::min<long>(2048, M / 8));
-            auto slab = at::empty({rsc_total * cs.Ko, S_},
-                                  x.options().dtype(at::kFloat));
-            if (cs.C == 1 && cs.R == 3 && cs.S == 3)
-                hipLaunchKernelGGL(k_wgrad_c1_r3, dim3(S_), dim3(256), 0,
-                                   stream.stream(), dyp, xp,
-                                   slab.data_ptr<float>(), cs, M, S_);
-            else
-            hipLaunchKernelGGL(k_wgrad_small_rsc, dim3(S_), dim3(256), 0,
-                               stream.stream(), dyp, xp,
-                               slab.data_ptr<float>(), cs, M, S_, rsc_total);
-            HIP_CHECK_LAST();
-            int total = rsc_total * cs.Ko;
-            hipLaunchKernelGGL(k_wgrad_small_rsc_combine,
-                               dim3(ceil_div_i(total, 4)), dim3(256), 0,
-                               stream.stream(), slab.data_ptr<float>(), S_,
-                               cs, rsc_total, dw.data_ptr<float>(),
-                               (float*)nullptr);
-            HIP_CHECK_LAST();
-            return {dw, unfused_bias()};
+            p.leaf = c1r3 ? WgradLeaf::C1R3 : WgradLeaf::SmallRsc;
+            p.S = (int)std::max<long>(1, std::min<long>(2048, M / 8));
+        } else {
+            p.leaf = WgradLeaf::SmallCin;
+            p.S = 64;
         }
-        int S_ = 64;
-        auto slab = at::empty({S_, rsc_total, cs.Ko},
-                              x.options().dtype(at::kFloat));
-        hipLaunchKernelGGL(k_wgrad_small_cin,
-                           dim3(rsc_total, S_, ceil_div_i(cs.Ko, 64)),
-                           dim3(256), 0, stream.stream(), dyp, xp,
-                           slab.data_ptr<float>(), cs, M, S_);
-        HIP_CHECK_LAST();
-        int total = rsc_total * cs.Ko;
-        hipLaunchKernelGGL(k_wgrad_small_combine,
-                           dim3(ceil_div_i(total, 256)), dim3(256), 0,
-                           stream.stream(), slab.data_ptr<float>(), S_, cs,
-                           rsc_total, dw.data_ptr<float>());
-        HIP_CHECK_LAST();
-        return {dw, unfused_bias()};
+        return p;
     }
 
     TORCH_CHECK(cs.C % 8 == 0 && cs.Ko % 8 == 0);
-    // Variant choice is MEASURED (profiles/, tools/bench_kernels.py):
-    //   * 128x128 wide tile, LDS-DMA staged (k_conv_wgrad_wide_dma),
-    //     64-deep, for big-Kgemm convs with enough tiles (with bias: conv3
-    //     119 vs 174 us pair-store, conv4 235 vs 384);
-    //   * the same tile 32-DEEP for small-Kgemm or tile-starved-but-deep-M
-    //     shapes (conv2 218 vs 282 us pair-store);
-    //   * 64x64 pair-store sb otherwise.  DDPX_WGRAD_V overrides
-    //     (w/wp/wq/w3/wx/wt/wt3/s/s6/sx/p); wp / wq are the pair-store
-    //     wide leaves the DMA leaf replaced (profiles/
-    //     toynet_b1024_1gpu_kernel_stats_wgraddma.md).
-    static const char* wv = getenv("DDPX_WGRAD_V");
-    const char sel = wv ? wv[0] : 0;
     const bool can_wide = cs.Ko >= 128 && Kgemm >= 128;
     const bool enough = can_wide &&
         (ceil_div_i(cs.Ko, 128) * ceil_div_i(Kgemm, 128) >= 8
          || M >= 262144);
-    const bool use_wide = (sel ? sel == 'w' : enough) && can_wide;
-    const bool use_sb = sel ? (sel == 's' || (sel == 'w' && !can_wide))
-                            : !enough;
-    const bool depth64_auto = Kgemm >= 1152;
-    const bool wide64 = use_wide && !(wv && wv[1] == '3');  // w32 forces 32
-    const int depth = use_wide ? (wide64 ? 64 : SBK) : (use_sb ? SBK : WBK);
-    const int tm = use_wide ? 128 : WBM, tn = use_wide ? 128 : WBN;
-    int gk = ceil_div_i(cs.Ko, tm), gr = ceil_div_i(Kgemm, tn);
-    int S_ = 1;
+    const bool wide = force == Auto
+        ? enough
+        : can_wide && force != Sb32 && force != Sb64;
+    const int tile = wide ? 128 : WBM;
+    p.gk = ceil_div_i(cs.Ko, tile);
+    p.gr = ceil_div_i(Kgemm, tile);
+    if (wide) {
+        const bool deep = Kgemm >= 1152;
+        p.leaf = force == Pair64 ? WgradLeaf::WidePair64
+               : force == Pair32 ? WgradLeaf::WidePair32
+               : force == Dma32 || !deep ? WgradLeaf::WideDma32
+               : WgradLeaf::WideDma64;
+    } else {
+        // single-ko-tile shapes: 64-deep staging measured faster (1x1
+        // [64x64,M=800k] 166 vs 174 us; 7x7 stem 209 vs 215)
+        const bool sb64 = force == Auto ? p.gk == 1 && p.gr <= 8
+                                        : force == Sb64;
+        p.leaf = sb64 ? WgradLeaf::SbPair64 : WgradLeaf::SbPair32;
+    }
+    // The loop counts contraction steps 64 deep for EVERY wide leaf and 32
+    // deep for EVERY sb leaf, whatever the leaf's own DEPTH (wide_dma<32>,
+    // wide_pair<32> and sb_pair<64> included).  Odd, but S fixes the
+    // summation order and so the bits of dw; the exact tests pin it.
+    const int count_depth = wide ? 64 : 32;
+    p.S = 1;
     // split until the machine fills (256 CUs x several blocks); small tile
     // grids (1x1 convs: one 64x64 tile) need deep splits — measured 17
     // TFLOP/s at the old S<=64 cap on [Ko=64,C=64] wgrad
@@ -2151,125 +1861,144 @@ static std::vector<at::Tensor> wgrad_impl(const at::Tensor& dy,
     // block (measured: S=512 at M=65k quadrupled a 55 us wgrad)
     // (cap 2048 measured worse: the S-sweep in the combine pass dominates
     // — 281 vs 174 us at [Ko=64,C=64,M=800k])
-    while (gk * gr * S_ < 1024 && S_ < 512 &&
-           M / ((long)S_ * 2 * depth) >= 8) S_ *= 2;
-    // which leaf runs (same order as the launch chain below)
-    const bool wide_pair = !wv || wv[1] == 'p' || wv[1] == 0;
-    // LDS-DMA staged leaf: the automatic choice for both wide classes;
-    // wt = the same by letter, wt3 = forced 32-deep
-    const bool leaf_dma = use_wide && (!wv || wv[1] == 't');
-    const bool leaf_dma32 = leaf_dma &&
-        ((wv && wv[2] == '3') || !depth64_auto);
-    const bool leaf_wp32 = !leaf_dma && use_wide &&
-        (wv ? wv[1] == 'q' : !depth64_auto);
-    const bool leaf_wp64 = !leaf_dma && !leaf_wp32 && use_wide && wide64 &&
-        wide_pair;
-    // the wide_pair and wide_dma leaves emit S_ x Ko bias partials behind
-    // the dw slices
-    const bool fused_bias = want_bias && (leaf_wp32 || leaf_wp64 || leaf_dma);
-    const long total = (long)cs.Ko * Kgemm;
-    const long bias_ld = fused_bias ? cs.Ko : 0;
-    auto slab = at::empty({S_ * (total + bias_ld)},
-                          x.options().dtype(at::kFloat));
+    while (p.gk * p.gr * p.S < 1024 && p.S < 512 &&
+           M / ((long)p.S * 2 * count_depth) >= 8) p.S *= 2;
+    // the wide leaves emit S x Ko bias partials behind the dw slices
+    p.fused_bias = want_bias && wide;
+    return p;
+}
+
+// (leaf name, split, fused_bias) that conv2d_wgrad / conv2d_wgrad_bias would
+// run for this shape under this process's DDPX_WGRAD_V; launches nothing
+std::tuple<std::string, long, bool> conv2d_wgrad_plan(
+        long N, long C, long H, long W, long Ko, long R, long S, long stride,
+        long pad, bool want_bias) {
+    TORCH_CHECK(N > 0 && C > 0 && Ko > 0 && R > 0 && S > 0 && stride > 0 &&
+                pad >= 0 && H + 2 * pad >= R && W + 2 * pad >= S);
+    ConvShape cs = make_shape((int)N, (int)C, (int)H, (int)W, (int)Ko, (int)R,
+                              (int)S, (int)stride, (int)pad);
+    WgradPlan p = plan_wgrad(cs, (long)cs.N * cs.P * cs.Q, want_bias,
+                             wgrad_override());
+    return std::make_tuple(std::string(WGRAD_LEAVES[(int)p.leaf].name),
+                           (long)p.S, p.fused_bias);
+}
+
+// dw, and with want_bias also db = sum of dy over (n, p, q): plan, allocate,
+// launch, combine.  The leaves Toy_Net runs (wide_dma<32>, wide_dma<64>, the
+// streaming stem kernel) produce db inside the wgrad and combine launches;
+// every other leaf takes the separate column-sum pass over dy.
+static std::vector<at::Tensor> wgrad_impl(const at::Tensor& dy,
+                                          const at::Tensor& x, long R,
+                                          long S, long stride, long pad,
+                                          bool want_bias) {
+    ConvShape cs = make_shape(x, dy.size(1), (int)R, (int)S, (int)stride,
+                              (int)pad);
+    TORCH_CHECK(cs.P == dy.size(2) && cs.Q == dy.size(3));
+    const long M = (long)cs.N * cs.P * cs.Q;
+    const int Kgemm = cs.R * cs.S * cs.C;
+    const WgradPlan plan = plan_wgrad(cs, M, want_bias, wgrad_override());
+    const int S_ = plan.S;
+    const bool fused_bias = plan.fused_bias;
+
+    auto stream = at::hip::getCurrentHIPStream();
+    const auto f32 = x.options().dtype(at::kFloat);
+    auto dw = at::empty({(long)cs.Ko, (long)cs.C, (long)cs.R, (long)cs.S},
+                        f32);
     at::Tensor db;
-    if (fused_bias)
-        db = at::empty({(long)cs.Ko}, x.options().dtype(at::kFloat));
-    // DDPX_WGRAD_V=wp/wq select the pair-store wide (conv4 373 vs 461 us,
-    // conv3 165 vs 210 against the scalar-store wide that plain w3/wx run)
-    if (leaf_dma32 && fused_bias)
-        hipLaunchKernelGGL((k_conv_wgrad_wide_dma<32, true>),
-                           dim3(gk, gr, S_), dim3(256), 0, stream.stream(),
-                           dyp, xp, slab.data_ptr<float>(), cs, M, Kgemm, S_);
-    else if (leaf_dma32)
-        hipLaunchKernelGGL((k_conv_wgrad_wide_dma<32>), dim3(gk, gr, S_),
-                           dim3(256), 0, stream.stream(), dyp, xp,
-                           slab.data_ptr<float>(), cs, M, Kgemm, S_);
-    else if (leaf_dma && fused_bias)
-        hipLaunchKernelGGL((k_conv_wgrad_wide_dma<64, true>),
-                           dim3(gk, gr, S_), dim3(256), 0, stream.stream(),
-                           dyp, xp, slab.data_ptr<float>(), cs, M, Kgemm, S_);
-    else if (leaf_dma)
-        hipLaunchKernelGGL((k_conv_wgrad_wide_dma<64>), dim3(gk, gr, S_),
-                           dim3(256), 0, stream.stream(), dyp, xp,
-                           slab.data_ptr<float>(), cs, M, Kgemm, S_);
-    else if (leaf_wp32 && fused_bias)
-        hipLaunchKernelGGL((k_conv_wgrad_wide_pair<32, true>),
-                           dim3(gk, gr, S_), dim3(256), 0, stream.stream(),
-                           dyp, xp, slab.data_ptr<float>(), cs, M, Kgemm, S_);
-    else if (leaf_wp32)
-        hipLaunchKernelGGL((k_conv_wgrad_wide_pair<32>), dim3(gk, gr, S_),
-                           dim3(256), 0, stream.stream(), dyp, xp,
-                           slab.data_ptr<float>(), cs, M, Kgemm, S_);
-    else if (leaf_wp64 && fused_bias)
-        hipLaunchKernelGGL((k_conv_wgrad_wide_pair<64, true>),
-                           dim3(gk, gr, S_), dim3(256), 0, stream.stream(),
-                           dyp, xp, slab.data_ptr<float>(), cs, M, Kgemm, S_);
-    else if (leaf_wp64)
-        hipLaunchKernelGGL((k_conv_wgrad_wide_pair<64>), dim3(gk, gr, S_),
-                           dim3(256), 0, stream.stream(), dyp, xp,
-                           slab.data_ptr<float>(), cs, M, Kgemm, S_);
-    else if (use_wide && wide64)
-        hipLaunchKernelGGL((k_conv_wgrad_wide<64>), dim3(gk, gr, S_),
-                           dim3(256), 0, stream.stream(), dyp, xp,
-                           slab.data_ptr<float>(), cs, M, Kgemm, S_);
-    else if (use_wide)
-        hipLaunchKernelGGL((k_conv_wgrad_wide<32>), dim3(gk, gr, S_),
-                           dim3(256), 0, stream.stream(), dyp, xp,
-                           slab.data_ptr<float>(), cs, M, Kgemm, S_);
-    else if (use_sb && (wv ? wv[1] == '6' : (gk == 1 && gr <= 8)))
-        // single-ko-tile shapes: 64-deep staging measured faster (1x1
-        // [64x64,M=800k] 166 vs 174 us; 7x7 stem 209 vs 215)
-        hipLaunchKernelGGL((k_conv_wgrad_sb_pair<64>), dim3(gk, gr, S_),
-                           dim3(256), 0, stream.stream(), dyp, xp,
-                           slab.data_ptr<float>(), cs, M, Kgemm, S_);
-    else if (use_sb && !(wv && wv[1] == 'x'))
-        hipLaunchKernelGGL((k_conv_wgrad_sb_pair<32>), dim3(gk, gr, S_),
-                           dim3(256), 0, stream.stream(), dyp, xp,
-                           slab.data_ptr<float>(), cs, M, Kgemm, S_);
-    else if (use_sb)
-        hipLaunchKernelGGL(k_conv_wgrad_sb, dim3(gk, gr, S_), dim3(256), 0,
-                           stream.stream(), dyp, xp, slab.data_ptr<float>(),
-                           cs, M, Kgemm, S_);
-    else
-        hipLaunchKernelGGL(k_conv_wgrad, dim3(gk, gr, S_), dim3(256), 0,
-                           stream.stream(), dyp, xp, slab.data_ptr<float>(),
-                           cs, M, Kgemm, S_);
-    HIP_CHECK_LAST();
-    at::Tensor slab_f = slab;
-    int S_c = S_;
+    if (fused_bias) db = at::empty({(long)cs.Ko}, f32);
     float* dbp = fused_bias ? db.data_ptr<float>() : nullptr;
-    if (S_ > 16) {
-        constexpr int CH = 8;
-        const int chunks = ceil_div_i(S_, CH);
-        auto slab2 = at::empty({chunks * (total + bias_ld)},
-                               x.options().dtype(at::kFloat));
-        const int blocks1 = (int)((total + bias_ld + 255) / 256);
-        if (fused_bias)
-            hipLaunchKernelGGL(k_wgrad_combine_stage<true>,
-                               dim3(blocks1, chunks), dim3(256), 0,
-                               stream.stream(), slab.data_ptr<float>(), S_,
-                               CH, total, cs.Ko, slab2.data_ptr<float>());
-        else
-            hipLaunchKernelGGL(k_wgrad_combine_stage<false>,
-                               dim3(blocks1, chunks), dim3(256), 0,
-                               stream.stream(), slab.data_ptr<float>(), S_,
-                               CH, total, cs.Ko, slab2.data_ptr<float>());
+    const bf16* dyp = reinterpret_cast<const bf16*>(dy.data_ptr());
+    const bf16* xp = reinterpret_cast<const bf16*>(x.data_ptr());
+
+    switch (plan.leaf) {
+    case WgradLeaf::StemStream:
+    case WgradLeaf::C1R3:
+    case WgradLeaf::SmallRsc: {
+        // slab [taps][Ko][S_], one combine for all three; the stem kernel
+        // with bias carries db as one more "tap"
+        const int nt = Kgemm + fused_bias;
+        auto slab = at::empty({nt * cs.Ko, S_}, f32);
+        if (plan.leaf == WgradLeaf::StemStream) {
+            const int rpl = 64 / (cs.Ko / 8);
+            const long nloads = (M + rpl - 1) / rpl;
+            const long chunk = (nloads + 4L * S_ - 1) / (4L * S_) * rpl;
+            auto kern = want_bias
+                ? (cs.pad ? k_wgrad_c1_r3_stream<true, true>
+                          : k_wgrad_c1_r3_stream<true, false>)
+                : (cs.pad ? k_wgrad_c1_r3_stream<false, true>
+                          : k_wgrad_c1_r3_stream<false, false>);
+            hipLaunchKernelGGL(kern, dim3(S_), dim3(256), 0, stream.stream(),
+                               dyp, xp, slab.data_ptr<float>(), cs, M, chunk);
+        } else if (plan.leaf == WgradLeaf::C1R3) {
+            hipLaunchKernelGGL(k_wgrad_c1_r3, dim3(S_), dim3(256), 0,
+                               stream.stream(), dyp, xp,
+                               slab.data_ptr<float>(), cs, M, S_);
+        } else {
+            hipLaunchKernelGGL(k_wgrad_small_rsc, dim3(S_), dim3(256), 0,
+                               stream.stream(), dyp, xp,
+                               slab.data_ptr<float>(), cs, M, S_, Kgemm);
+        }
         HIP_CHECK_LAST();
-        slab_f = slab2;
-        S_c = chunks;
+        hipLaunchKernelGGL(k_wgrad_small_rsc_combine,
+                           dim3(ceil_div_i(nt * cs.Ko, 4)), dim3(256), 0,
+                           stream.stream(), slab.data_ptr<float>(), S_, cs,
+                           Kgemm, dw.data_ptr<float>(), dbp);
+        HIP_CHECK_LAST();
+        break;
     }
-    int blocks = std::min<long>(4096, ceil_div_i(total, 256));
-    if (fused_bias)
-        hipLaunchKernelGGL(k_wgrad_combine<true>, dim3(blocks + 1),
-                           dim3(256), 0, stream.stream(),
-                           slab_f.data_ptr<float>(), S_c, cs, Kgemm,
-                           dw.data_ptr<float>(), dbp);
-    else
-        hipLaunchKernelGGL(k_wgrad_combine<false>, dim3(blocks), dim3(256),
-                           0, stream.stream(), slab_f.data_ptr<float>(), S_c,
+    case WgradLeaf::SmallCin: {
+        auto slab = at::empty({S_, Kgemm, cs.Ko}, f32);
+        hipLaunchKernelGGL(k_wgrad_small_cin,
+                           dim3(Kgemm, S_, ceil_div_i(cs.Ko, 64)), dim3(256),
+                           0, stream.stream(), dyp, xp,
+                           slab.data_ptr<float>(), cs, M, S_);
+        HIP_CHECK_LAST();
+        hipLaunchKernelGGL(k_wgrad_small_combine,
+                           dim3(ceil_div_i(Kgemm * cs.Ko, 256)), dim3(256), 0,
+                           stream.stream(), slab.data_ptr<float>(), S_, cs,
+                           Kgemm, dw.data_ptr<float>());
+        HIP_CHECK_LAST();
+        break;
+    }
+    default: {
+        // MFMA leaves: S_ slices of [Ko][Kgemm], then (fused bias) S_ x Ko
+        // bias partials; past 16 slices the combine runs in two stages
+        const long total = (long)cs.Ko * Kgemm;
+        const long bias_ld = fused_bias ? cs.Ko : 0;
+        auto slab = at::empty({S_ * (total + bias_ld)}, f32);
+        hipLaunchKernelGGL(WGRAD_LEAVES[(int)plan.leaf].kern[fused_bias],
+                           dim3(plan.gk, plan.gr, S_), dim3(256), 0,
+                           stream.stream(), dyp, xp, slab.data_ptr<float>(),
+                           cs, M, Kgemm, S_);
+        HIP_CHECK_LAST();
+        at::Tensor slab_f = slab;
+        int S_c = S_;
+        if (S_ > 16) {
+            constexpr int CH = 8;
+            const int chunks = ceil_div_i(S_, CH);
+            auto slab2 = at::empty({chunks * (total + bias_ld)}, f32);
+            const int blocks1 = (int)((total + bias_ld + 255) / 256);
+            auto stage = fused_bias ? k_wgrad_combine_stage<true>
+                                    : k_wgrad_combine_stage<false>;
+            hipLaunchKernelGGL(stage, dim3(blocks1, chunks), dim3(256), 0,
+                               stream.stream(), slab.data_ptr<float>(), S_,
+                               CH, total, cs.Ko, slab2.data_ptr<float>());
+            HIP_CHECK_LAST();
+            slab_f = slab2;
+            S_c = chunks;
+        }
+        // fused bias: one block more, which sums the bias partials
+        const int blocks = std::min<long>(4096, ceil_div_i(total, 256));
+        auto combine = fused_bias ? k_wgrad_combine<true>
+                                  : k_wgrad_combine<false>;
+        hipLaunchKernelGGL(combine, dim3(blocks + fused_bias), dim3(256), 0,
+                           stream.stream(), slab_f.data_ptr<float>(), S_c,
                            cs, Kgemm, dw.data_ptr<float>(), dbp);
-    HIP_CHECK_LAST();
-    if (want_bias && !fused_bias) db = unfused_bias();
+        HIP_CHECK_LAST();
+    }
+    }
+    if (want_bias && !fused_bias)
+        db = col_sum(dy.permute({0, 2, 3, 1}).reshape({M, (long)cs.Ko}));
     return {dw, db};
 }
 
@@ -2284,42 +2013,4 @@ std::vector<at::Tensor> conv2d_wgrad_bias(at::Tensor dy, at::Tensor x,
                                           long R, long S, long stride,
                                           long pad) {
     return wgrad_impl(dy, x, R, S, stride, pad, true);
-}
-
-
-std::vector<at::Tensor> conv2d_fwd_stats(at::Tensor x, at::Tensor w,
-                                         c10::optional<at::Tensor> bias,
-                                         long stride, long pad) {
-    // forward conv + per-channel partial stats for the consuming BN
-    // (SURVEY §7 "fuse normalisation work into the producing kernel")
-    TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16);
-    ConvShape cs = make_shape(x, w.size(0), w.size(2), w.size(3),
-                              (int)stride, (int)pad);
-    TORCH_CHECK(cs.C % 8 == 0, "stats path needs the MFMA conv (C%8==0)");
-    TORCH_CHECK(cs.Ko % 8 == 0, "conv fwd needs Ko % 8 == 0");
-    int Kgemm = cs.R * cs.S * cs.C;
-    long M = (long)cs.N * cs.P * cs.Q;
-    auto y = at::empty({cs.N, cs.Ko, cs.P, cs.Q},
-                       x.options().memory_format(at::MemoryFormat::ChannelsLast));
-    auto stream = at::hip::getCurrentHIPStream();
-    const float* bp = bias.has_value() ? bias->data_ptr<float>() : nullptr;
-    const bf16* xp = reinterpret_cast<const bf16*>(x.data_ptr());
-    const bf16* wp = reinterpret_cast<const bf16*>(w.data_ptr());
-    bf16* yp = reinterpret_cast<bf16*>(y.data_ptr());
-    int gridM = ceil_div_i(M, CBM);
-    auto slab = at::empty({2, (long)cs.Ko, (long)gridM},
-                          x.options().dtype(at::kFloat));
-    if (cs.Ko >= 128) {
-        dim3 grid(gridM, ceil_div_i(cs.Ko, 128));
-        hipLaunchKernelGGL((k_conv_gemm<0, 128, 2, 2>), grid, dim3(256), 0,
-                           stream.stream(), xp, wp, bp, yp, cs, (int)M,
-                           Kgemm, cs.Ko, slab.data_ptr<float>());
-    } else {
-        dim3 grid(gridM, ceil_div_i(cs.Ko, 64));
-        hipLaunchKernelGGL((k_conv_gemm<0, 64, 4, 1>), grid, dim3(256), 0,
-                           stream.stream(), xp, wp, bp, yp, cs, (int)M,
-                           Kgemm, cs.Ko, slab.data_ptr<float>());
-    }
-    HIP_CHECK_LAST();
-    return {y, slab};
 }

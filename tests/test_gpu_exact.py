@@ -334,30 +334,37 @@ def test_small_cin_autograd_grads_exact(shape):
 
 # ------------------------------------------------------------- conv wgrad ---
 
-WGRAD_SHAPES = [
-    (2, 8, 5, 7, 8, 3, 3, 1, 1),      # sb_pair<64>, S_ = 1
-    (4, 8, 64, 65, 8, 1, 1, 1, 0),    # sb_pair<64>, M=16640: S_=64 > 16 ->
-                                      # two-stage combine; M % (64*64) != 0
-    (2, 8, 6, 6, 72, 3, 3, 1, 1),     # sb_pair<32>, gk = 2
-    (2, 56, 6, 5, 136, 3, 3, 1, 1),   # wide_pair<32>; Ko, Kgemm=504 tails
-    (2, 128, 5, 6, 128, 3, 3, 1, 1),  # wide_pair<64>, Kgemm = 1152
-    (2, 136, 5, 6, 136, 3, 3, 1, 1),  # wide_pair<64> with tails
-    (2, 16, 10, 13, 32, 3, 3, 3, 1),  # stride 3
-    (2, 8, 12, 10, 64, 3, 1, 2, 0),   # R != S
-    (1, 1, 3, 3, 8, 3, 3, 1, 0),      # k_wgrad_c1_r3, M = 1, S_ = 1
-    (3, 1, 7, 9, 8, 3, 3, 1, 1),      # k_wgrad_c1_r3, padded
-    (3, 1, 9, 8, 16, 3, 3, 2, 0),     # k_wgrad_c1_r3, stride 2
-    (2, 3, 6, 8, 16, 2, 2, 1, 0),     # k_wgrad_small_rsc, rsc = 12
-    (2, 1, 7, 6, 8, 4, 4, 1, 1),      # k_wgrad_small_rsc, rsc = 16
-    (2, 3, 7, 6, 16, 3, 3, 1, 1),     # k_wgrad_small_cin, rsc = 27
-    (2, 1, 6, 7, 72, 3, 3, 1, 1),     # k_wgrad_small_cin, Ko > 64
-    (2, 3, 7, 6, 136, 3, 3, 1, 0),    # k_wgrad_small_cin, Ko > 64
+# shape, the leaf name conv2d_wgrad_plan must report for it, and the split
+# where the row is there for it (None: not asserted)
+_WGRAD_ROWS = [
+    ((2, 8, 5, 7, 8, 3, 3, 1, 1), "sb_pair<64>", 1),
+    ((4, 8, 64, 65, 8, 1, 1, 1, 0), "sb_pair<64>", 64),  # M=16640: S_ > 16
+                                # -> two-stage combine; M % (64*64) != 0
+    ((2, 8, 6, 6, 72, 3, 3, 1, 1), "sb_pair<32>", None),    # gk = 2
+    ((2, 56, 6, 5, 136, 3, 3, 1, 1), "wide_dma<32>", None),  # Ko, Kgemm=504
+                                                             # tails
+    ((2, 128, 5, 6, 128, 3, 3, 1, 1), "wide_dma<64>", None),  # Kgemm = 1152
+    ((2, 136, 5, 6, 136, 3, 3, 1, 1), "wide_dma<64>", None),  # with tails
+    ((2, 16, 10, 13, 32, 3, 3, 3, 1), "sb_pair<64>", None),   # stride 3
+    ((2, 8, 12, 10, 64, 3, 1, 2, 0), "sb_pair<64>", None),    # R != S
+    ((1, 1, 3, 3, 8, 3, 3, 1, 0), "c1_r3_stream", 1),         # M = 1
+    ((3, 1, 7, 9, 8, 3, 3, 1, 1), "c1_r3_stream", None),      # padded
+    ((3, 1, 9, 8, 16, 3, 3, 2, 0), "c1_r3_stream", None),     # stride 2
+    ((2, 3, 6, 8, 16, 2, 2, 1, 0), "small_rsc", None),        # rsc = 12
+    ((2, 1, 7, 6, 8, 4, 4, 1, 1), "small_rsc", None),         # rsc = 16
+    ((2, 3, 7, 6, 16, 3, 3, 1, 1), "small_cin", None),        # rsc = 27
+    ((2, 1, 6, 7, 72, 3, 3, 1, 1), "small_cin", None),        # Ko > 64
+    ((2, 3, 7, 6, 136, 3, 3, 1, 0), "small_cin", None),       # Ko > 64
 ]
 
 
-@pytest.mark.parametrize("shape", WGRAD_SHAPES)
-def test_conv_wgrad_exact(shape):
+@pytest.mark.parametrize("shape,leaf,split", _WGRAD_ROWS,
+                         ids=[f"shape{i}" for i in range(len(_WGRAD_ROWS))])
+def test_conv_wgrad_exact(shape, leaf, split):
     N, C, H, W, K, R, S, stride, pad = shape
+    got_leaf, got_split, _ = ext.conv2d_wgrad_plan(*shape, False)
+    assert got_leaf == leaf
+    assert split is None or got_split == split   # 64 > 16: two-stage combine
     P, Q = _out_hw(H, W, R, S, stride, pad)
     x = _ints((N, C, H, W), -2, 2, "x")
     dy = _ints((N, K, P, Q), -2, 2, "dy")

@@ -29,8 +29,9 @@ n < 5792, so gamma = (L + T) * u is rigorous for the sizes used here.
       L = ceil(nloads / (4*S))             serial fmaf chain per lane
       T = 4*rpl                            LDS sum of 4 waves x rpl rows
         + ceil(S/64) + 6                   combine: lane sweep + 6 shuffles
-  wide_pair<DEPTH> bias (DEPTH 32 for Kgemm < 1152, else 64), split S as
-  the host's loop picks it:
+  wide_pair<DEPTH> bias, which wide_dma<DEPTH>'s chain stays inside (DEPTH
+  32 for Kgemm < 1152, else 64), split S from the host's loop counted with
+  DEPTH (see _wide_pair_gamma for where the host's own S is smaller):
       L = ceil(ceil(M/DEPTH) / S) * DEPTH/2   half-row chain per thread
         + 1                                    the other half (shuffle)
       T = S                 if S <= 16         one serial combine
@@ -98,13 +99,21 @@ def _stem_gamma(M, Ko):
     return (L + T) * U
 
 
-def _wide_pair_gamma(M, Ko, Kgemm):
+def _wide_pair_gamma(M, Ko, Kgemm, count_depth=None):
+    """(gamma, S).  The host's split loop counts contraction steps 64 deep on
+    every wide leaf; ``count_depth=64`` gives that S, which the plan tests
+    below hold equal to conv2d_wgrad_plan's.  The default counts with the
+    leaf's own depth as this file always has: on a 32-deep row whose M ends
+    the loop it doubles once more, and that larger S makes gamma SMALLER
+    than the rigorous one (154u against 289u at M = 8320), so the bound
+    checks keep using it: they ask more, not less."""
     assert Ko >= 128 and Kgemm >= 128
     depth = 64 if Kgemm >= 1152 else 32
     tiles = _cdiv(Ko, 128) * _cdiv(Kgemm, 128)
     assert tiles >= 8 or M >= 262144, "shape does not reach wide_pair"
     S = 1
-    while tiles * S < 1024 and S < 512 and M // (S * 2 * depth) >= 8:
+    while (tiles * S < 1024 and S < 512
+           and M // (S * 2 * (count_depth or depth)) >= 8):
         S *= 2
     L = _cdiv(_cdiv(M, depth), S) * (depth // 2) + 1
     T = S if S <= 16 else 4 + 1 + _cdiv(S, 8)
@@ -130,34 +139,43 @@ def _case(shape, kind):
     return x, dy, dw, dw_abs, dy.sum((0, 2, 3)), dy.abs().sum((0, 2, 3))
 
 
-# shapes (N, C, H, W, K, R, S, stride, pad)
-LEAF_SHAPES = [
-    (2, 8, 5, 7, 8, 3, 3, 1, 1),      # sb_pair<64>, S_ = 1
-    (4, 8, 64, 65, 8, 1, 1, 1, 0),    # sb_pair<64>, two-stage combine
-    (2, 8, 6, 6, 72, 3, 3, 1, 1),     # sb_pair<32>, gk = 2
-    (2, 56, 6, 5, 136, 3, 3, 1, 1),   # wide_pair<32>; Ko, Kgemm=504 tails
-    (2, 128, 5, 6, 128, 3, 3, 1, 1),  # wide_pair<64>, Kgemm = 1152
-    (2, 136, 5, 6, 136, 3, 3, 1, 1),  # wide_pair<64> with tails
-    (2, 16, 10, 13, 32, 3, 3, 3, 1),  # stride 3
-    (2, 8, 12, 10, 64, 3, 1, 2, 0),   # R != S
-    (1, 1, 3, 3, 8, 3, 3, 1, 0),      # stem, M = 1, Ko = 8
-    (3, 1, 7, 9, 8, 3, 3, 1, 1),      # stem, padded
-    (3, 1, 9, 8, 16, 3, 3, 2, 0),     # stem, stride 2
-    (2, 3, 6, 8, 16, 2, 2, 1, 0),     # k_wgrad_small_rsc, rsc = 12
-    (2, 1, 7, 6, 8, 4, 4, 1, 1),      # k_wgrad_small_rsc, rsc = 16
-    (2, 3, 7, 6, 16, 3, 3, 1, 1),     # k_wgrad_small_cin, rsc = 27
-    (2, 1, 6, 7, 72, 3, 3, 1, 1),     # k_wgrad_small_cin, Ko > 64
-    (2, 3, 7, 6, 136, 3, 3, 1, 0),    # k_wgrad_small_cin, Ko > 64
-    (2, 1, 5, 6, 12, 3, 3, 1, 1),     # k_wgrad_c1_r3 (Ko % 8 != 0)
-    (4, 128, 64, 65, 128, 1, 1, 1, 0),  # M = 16640, split > 16, two-stage
-                                        # combine, M % (split*depth) != 0
+# shapes (N, C, H, W, K, R, S, stride, pad), each with the leaf name that
+# conv2d_wgrad_plan must report for it (test_rows_reach_the_leaf_they_name)
+_LEAF_ROWS = [
+    ((2, 8, 5, 7, 8, 3, 3, 1, 1), "sb_pair<64>"),      # S_ = 1
+    ((4, 8, 64, 65, 8, 1, 1, 1, 0), "sb_pair<64>"),    # two-stage combine
+    ((2, 8, 6, 6, 72, 3, 3, 1, 1), "sb_pair<32>"),     # gk = 2
+    ((2, 56, 6, 5, 136, 3, 3, 1, 1), "wide_dma<32>"),  # Ko, Kgemm=504 tails
+    ((2, 128, 5, 6, 128, 3, 3, 1, 1), "wide_dma<64>"),   # Kgemm = 1152
+    ((2, 136, 5, 6, 136, 3, 3, 1, 1), "wide_dma<64>"),   # with tails
+    ((2, 16, 10, 13, 32, 3, 3, 3, 1), "sb_pair<64>"),  # stride 3
+    ((2, 8, 12, 10, 64, 3, 1, 2, 0), "sb_pair<64>"),   # R != S
+    ((1, 1, 3, 3, 8, 3, 3, 1, 0), "c1_r3_stream"),     # M = 1, Ko = 8
+    ((3, 1, 7, 9, 8, 3, 3, 1, 1), "c1_r3_stream"),     # padded
+    ((3, 1, 9, 8, 16, 3, 3, 2, 0), "c1_r3_stream"),    # stride 2
+    ((2, 3, 6, 8, 16, 2, 2, 1, 0), "small_rsc"),       # rsc = 12
+    ((2, 1, 7, 6, 8, 4, 4, 1, 1), "small_rsc"),        # rsc = 16
+    ((2, 3, 7, 6, 16, 3, 3, 1, 1), "small_cin"),       # rsc = 27
+    ((2, 1, 6, 7, 72, 3, 3, 1, 1), "small_cin"),       # Ko > 64
+    ((2, 3, 7, 6, 136, 3, 3, 1, 0), "small_cin"),      # Ko > 64
+    ((2, 1, 5, 6, 12, 3, 3, 1, 1), "c1_r3"),           # Ko % 8 != 0
+    ((4, 128, 64, 65, 128, 1, 1, 1, 0), "sb_pair<32>"),  # M = 16640, split
+                        # > 16, two-stage combine, M % (split*depth) != 0
 ]
-# fused-bias leaves with split > 16: bias partials through BOTH combine
-# kernels, M no multiple of split * depth
-DEEP_WIDE_SHAPES = [
-    (2, 512, 64, 65, 256, 1, 1, 1, 0),   # wide_pair<32>, 8 tiles, M = 8320
-    (4, 128, 64, 65, 128, 3, 3, 1, 1),   # wide_pair<64>, 9 tiles, M = 16640
+LEAF_SHAPES = [shape for shape, _ in _LEAF_ROWS]
+# rows whose purpose is the two-stage combine: the plan's split must be > 16
+TWO_STAGE_SB_SHAPES = [LEAF_SHAPES[1], LEAF_SHAPES[17]]
+# fused-bias leaves at deep splits, M no multiple of split * depth.  The
+# host's split is 16 on the first row (it counts 64 deep, see
+# _wide_pair_gamma): the deepest ONE-stage combine.  On the other two it is
+# 32: bias partials through BOTH combine kernels, at either depth.
+_DEEP_WIDE_ROWS = [
+    ((2, 512, 64, 65, 256, 1, 1, 1, 0), "wide_dma<32>"),  # 8 tiles, M = 8320
+    ((4, 128, 64, 65, 128, 3, 3, 1, 1), "wide_dma<64>"),  # 9 tiles, M = 16640
+    ((16, 56, 33, 32, 136, 3, 3, 1, 1), "wide_dma<32>"),  # 8 tiles, M = 16896
 ]
+DEEP_WIDE_SHAPES = [shape for shape, _ in _DEEP_WIDE_ROWS]
+TWO_STAGE_WIDE_SHAPES = DEEP_WIDE_SHAPES[1:]
 STEM_SHAPES = [
     (1, 1, 3, 3, 64, 3, 3, 1, 0),     # M = 1
     (3, 1, 7, 9, 64, 3, 3, 1, 1),     # padded; row and image wraps inside
@@ -192,6 +210,36 @@ def test_shape_tables_reach_what_they_claim():
         _wide_pair_gamma(_m_kgemm(shape)[0], shape[4], _m_kgemm(shape)[1])
     for shape in STEM_SHAPES:
         assert shape[1] == 1 and shape[4] % 8 == 0 and shape[4] <= 64
+
+
+def _plan(shape, want_bias):
+    """(leaf name, split, fused_bias) from the host's own plan function."""
+    return ext.conv2d_wgrad_plan(*shape, want_bias)
+
+
+def test_rows_reach_the_leaf_they_name():
+    """Ask the host which leaf and split it launches, instead of guessing."""
+    rows = (_LEAF_ROWS + _DEEP_WIDE_ROWS
+            + [(shape, "c1_r3_stream") for shape in STEM_SHAPES])
+    for shape, leaf in rows:
+        fused = leaf.startswith(("wide_", "c1_r3_stream"))
+        for want_bias in (False, True):
+            got_leaf, _, got_fused = _plan(shape, want_bias)
+            assert got_leaf == leaf, (shape, got_leaf)
+            assert got_fused == (want_bias and fused), shape
+    for shape in TWO_STAGE_SB_SHAPES + TWO_STAGE_WIDE_SHAPES:
+        assert _plan(shape, True)[1] > 16, shape
+    for shape in TWO_STAGE_WIDE_SHAPES:
+        M, Kgemm = _m_kgemm(shape)
+        depth = 64 if Kgemm >= 1152 else 32
+        assert M % (_plan(shape, True)[1] * depth) != 0
+    assert _plan(DEEP_WIDE_SHAPES[0], True)[1] == 16
+    for shape in WIDE_PAIR_SHAPES:
+        M, Kgemm = _m_kgemm(shape)
+        rigorous, S = _wide_pair_gamma(M, shape[4], Kgemm, count_depth=64)
+        assert _plan(shape, True)[1] == _plan(shape, False)[1] == S, shape
+        # the gamma the bound checks use is never the larger one
+        assert _wide_pair_gamma(M, shape[4], Kgemm)[0] <= rigorous
 
 
 # ------------------------------------------------------------------ exact ---
@@ -277,7 +325,7 @@ def _autograd_grads(shape, x, w, b, dy):
 
 
 @pytest.mark.parametrize("shape,mfma", [
-    ((2, 56, 6, 5, 136, 3, 3, 1, 1), True),     # wide_pair<32>
+    ((2, 56, 6, 5, 136, 3, 3, 1, 1), True),     # wide_dma<32>
     ((5, 1, 28, 28, 64, 3, 3, 1, 0), False),    # streaming stem kernel
 ])
 def test_autograd_matches_col_sum_path(shape, mfma, monkeypatch):

@@ -59,6 +59,7 @@ SHAPES = [
 ]
 KINDS = ("int", "rand")
 LEAVES = ("wt", "wp", "wq")
+SMALLEST = (2, 8, 5, 7, 8, 3, 3, 1, 1)   # for the unknown-override child
 
 
 # ---------------------------------------------------------------- helpers ---
@@ -144,17 +145,28 @@ def _refs(shape, kind):
 
 def _child(out_path):
     """Runs every case this process's DDPX_WGRAD_V leaf is needed for and
-    saves {(shape, kind): (dw_plain, dw, db, dw2, db2)} as CPU tensors."""
+    saves {(shape, kind): (dw_plain, dw, db, dw2, db2)} as CPU tensors, and
+    {("plan", shape): conv2d_wgrad_plan's (leaf name, split, fused_bias)}.
+    A value that names no leaf (test_unknown_override_is_an_error) gets one
+    conv2d_wgrad call on SMALLEST, which must raise."""
     sys.path.insert(0, REPO)
     from ddp_tricks_amd.ops import load_extension
     ext = load_extension(required=True)
     dev = torch.device("cuda:0")
     leaf = os.environ["DDPX_WGRAD_V"]
+    if leaf not in LEAVES:
+        N, C, H, W, K, R, S, stride, pad = SMALLEST
+        x, dy = _inputs(SMALLEST, "int")
+        ext.conv2d_wgrad(_nhwc(dy.to(BF)).to(dev), _nhwc(x.to(BF)).to(dev),
+                         R, S, stride, pad)
+        torch.cuda.synchronize()
+        return
     out = {}
     for shape in SHAPES:
         if leaf != "wt" and leaf != _old_leaf(shape):
             continue
         N, C, H, W, K, R, S, stride, pad = shape
+        out[("plan", shape)] = ext.conv2d_wgrad_plan(*shape, True)
         for kind in KINDS:
             if leaf != "wt" and kind == "int":
                 continue
@@ -213,6 +225,38 @@ def test_shapes_reach_what_they_claim():
     while 8 * S < 1024 and S < 512 and M // (S * 128) >= 8:
         S *= 2
     assert M == 16896 and S > 16 and _cdiv(_cdiv(M, 32), S) > 1
+
+
+def test_children_ran_the_leaf_they_were_forced_to(leaf_out):
+    """What the host's own plan reported in each child."""
+    for shape in SHAPES:
+        depth = _depth(shape)
+        new, old = leaf_out["wt"], leaf_out[_old_leaf(shape)]
+        assert new[("plan", shape)][0] == f"wide_dma<{depth}>"
+        assert old[("plan", shape)][0] == f"wide_pair<{depth}>"
+        # same split and both with the bias fused: dw is comparable bit by bit
+        assert new[("plan", shape)][1:] == old[("plan", shape)][1:]
+        assert new[("plan", shape)][2] is True
+    # the split test_shapes_reach_what_they_claim works out for the last shape
+    M, _ = _m_kgemm(SHAPES[5])
+    S = 1
+    while 8 * S < 1024 and S < 512 and M // (S * 128) >= 8:
+        S *= 2
+    assert leaf_out["wt"][("plan", SHAPES[5])][1] == S
+
+
+def test_unknown_override_is_an_error(tmp_path):
+    """A DDPX_WGRAD_V value that names no leaf must stop the first wgrad call
+    with the accepted spellings, not run some other kernel silently."""
+    env = dict(os.environ)
+    env["DDPX_WGRAD_V"] = "zz"
+    p = subprocess.run(
+        [sys.executable, os.path.abspath(__file__), "--child",
+         str(tmp_path / "zz.pt")],
+        cwd=REPO, env=env, capture_output=True, text=True, timeout=240)
+    assert p.returncode != 0, p.stderr[-2000:]
+    assert "DDPX_WGRAD_V=zz" in p.stderr, p.stderr[-2000:]
+    assert "wt, wt3, wp, wq, s, sb, s6" in p.stderr, p.stderr[-2000:]
 
 
 @pytest.mark.parametrize("shape", SHAPES)

@@ -8,8 +8,11 @@ Usage (on a GPU box):  python tools/bench_kernels.py [--resnet]
 
 Times conv fwd/dgrad/wgrad per shape with HIP events (200 reps after 20
 warmup) and prints achieved TFLOP/s next to microseconds, so kernel A/B
-decisions are measurements, not guesses.  DDPX_WGRAD_V=sb selects the
-single-buffer wgrad variant for comparison.
+decisions are measurements, not guesses.  DDPX_WGRAD_V forces a conv wgrad
+leaf for comparison: wt / wt3 (wide_dma at the automatic depth / 32-deep),
+wp / wq (wide_pair 64- / 32-deep), s or sb / s6 (sb_pair 32- / 64-deep).
+The extension rejects every other value, so --leaves takes only these
+spellings; a child given anything else stops at its first wgrad call.
 """
 import argparse
 import os
