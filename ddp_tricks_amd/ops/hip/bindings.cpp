@@ -90,7 +90,10 @@ std::vector<at::Tensor> conv2d_fwd_stats(at::Tensor x, at::Tensor w,
                                          long stride, long pad);
 at::Tensor conv2d_dgrad(at::Tensor dy, at::Tensor wt2, long N, long C, long H,
                         long W, long R, long S, long stride, long pad,
-                        c10::optional<at::Tensor> addend);
+                        c10::optional<at::Tensor> addend, long group);
+std::tuple<std::string, long, long, long> conv2d_dgrad_plan(
+    long N, long C, long H, long W, long Ko, long R, long S, long stride,
+    long pad, long group);
 std::vector<at::Tensor> conv2d_dgrad_bn(at::Tensor dy, at::Tensor wt2,
                                         long N, long C, long H, long W,
                                         long R, long S, long pad,
@@ -202,7 +205,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("dy"), py::arg("wt2"), py::arg("N"), py::arg("C"),
           py::arg("H"), py::arg("W"), py::arg("R"), py::arg("S"),
           py::arg("stride"), py::arg("pad"),
-          py::arg("addend") = c10::nullopt);
+          py::arg("addend") = c10::nullopt, py::arg("group") = -1);
+    m.def("conv2d_dgrad_plan", &conv2d_dgrad_plan,
+          "(name, G, k_tiles_issued, k_tiles_raster) conv2d_dgrad would run "
+          "for this shape; group -1 automatic, 0 raster, 32/64/128 forces "
+          "that tap-uniform group size; launches nothing",
+          py::arg("N"), py::arg("C"), py::arg("H"), py::arg("W"),
+          py::arg("Ko"), py::arg("R"), py::arg("S"), py::arg("stride"),
+          py::arg("pad"), py::arg("group") = -1);
     m.def("conv2d_dgrad_bn", &conv2d_dgrad_bn);
     m.def("conv2d_wgrad", &conv2d_wgrad);
     m.def("conv2d_wgrad_bias", &conv2d_wgrad_bias);

@@ -37,12 +37,51 @@ struct ConvShape {
     int off_r[4], off_s[4];     // p = h' + off_r[ri], q = w' + off_s[si]
     int Hfull, Wfull;           // original dx dims (epilogue scatter)
     FastDiv fdNs;
+    // MODE 1 tap-uniform row order (TAPS): GEMM rows run (group, pixel,
+    // image-in-group) with G = 1 << lgG images per group; fdGHW divides by
+    // G*H*W.
+    FastDiv fdGHW;
+    int lgG;
 };
 
 static inline void init_fastdiv(ConvShape& cs) {
     cs.fdQ.init(cs.Q); cs.fdP.init(cs.P); cs.fdW.init(cs.W);
     cs.fdH.init(cs.H); cs.fdC.init(cs.C); cs.fdS.init(cs.S);
     cs.fdKo.init(cs.Ko);
+    cs.fdGHW.init(1); cs.lgG = 0;
+}
+
+// Tap-uniform dgrad rows (TAPS): the (r, s) taps that land inside dy for at
+// least one dx pixel among GEMM rows [m_first, m_last]; bit r*S + s.  Rows
+// decode as grp = m / GHW, pix = (m % GHW) >> lgG, so a tile inside one image
+// group covers the contiguous pixel range [pix0, pix1]; a tile that crosses
+// a group boundary takes the whole image.  Tap (r, s) reaches dy from pixel
+// (h, w) iff 0 <= h + pad - r < P and 0 <= w + pad - s < Q.  ONE function for
+// the kernel's K-loop mask and the host's tile count (conv2d_dgrad_plan).
+__host__ __device__ inline unsigned dgrad_tap_mask(
+        int m_first, int m_last, int GHW, int lgG, int H, int W, int P, int Q,
+        int R, int S, int pad) {
+    const int g0 = m_first / GHW, g1 = m_last / GHW;
+    int pix0 = 0, pix1 = H * W - 1;
+    if (g0 == g1) {
+        pix0 = (m_first - g0 * GHW) >> lgG;
+        pix1 = (m_last - g0 * GHW) >> lgG;
+    }
+    const int h0 = pix0 / W, h1 = pix1 / W;
+    unsigned mask = 0;
+    for (int h = h0; h <= h1; ++h) {
+        // columns of this image row inside the pixel range
+        const int wa = h == h0 ? pix0 - h0 * W : 0;
+        const int wb = h == h1 ? pix1 - h1 * W : W - 1;
+        const int ra = h + pad - P + 1 > 0 ? h + pad - P + 1 : 0;
+        const int rb = h + pad < R - 1 ? h + pad : R - 1;
+        const int sa = wa + pad - Q + 1 > 0 ? wa + pad - Q + 1 : 0;
+        const int sb = wb + pad < S - 1 ? wb + pad : S - 1;
+        for (int r = ra; r <= rb; ++r)
+            for (int sx = sa; sx <= sb; ++sx)
+                mask |= 1u << (r * S + sx);
+    }
+    return mask;
 }
 
 // ---------------------------------------------------------------- forward ---
@@ -85,7 +124,7 @@ struct BnFuse {
 // skip-gradient accumulation fused into the junction conv's dgrad
 // (VERDICT r01 next-round #4).
 template <int MODE, int TBN, int WAVES_M, int WAVES_N, bool STRIDE1,
-          int CBM_T>
+          int CBM_T, bool TAPS = false>
 __device__ __forceinline__
 void conv_gemm_body(const bf16* __restrict__ Asrc,
                     const bf16* __restrict__ Bsrc,
@@ -106,7 +145,16 @@ void conv_gemm_body(const bf16* __restrict__ Asrc,
     // guide's 256^2-tile GEMM that runs ~1 block/CU.
     __shared__ bf16 lds_a[1][CBM_T][CBK];  // unpadded: glds dest is linear
     __shared__ bf16 lds_b[1][TBN][CBK];
-    const int m0 = blockIdx.x * CBM_T;
+    static_assert(!TAPS || (MODE == 1 && STRIDE1), "TAPS is stride-1 dgrad");
+    // TAPS: consecutive blockIdx.x land on different XCDs (b and b + 8 share
+    // one), so where the tile count divides, hand XCD j the j-th eighth of
+    // the tiles — the blocks resident on one XCD then walk neighbouring
+    // pixels of one image group and share their dy reads in that XCD's L2.
+    // Measured: without it conv4 at G = 128 is 264.8 us, with it 230.5.
+    const int tile_m = TAPS && (gridDim.x & 7) == 0
+        ? (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3)
+        : (int)blockIdx.x;
+    const int m0 = tile_m * CBM_T;
     const int n0 = blockIdx.y * TBN;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -149,6 +197,17 @@ void conv_gemm_body(const bf16* __restrict__ Asrc,
                 ri_nb[ci] = (long)n * cs.P;
                 ri_u[ci] = h1;
                 ri_v[ci] = w1;
+            } else if (TAPS) {
+                // (group, pixel, image-in-group) order: see dgrad_tap_mask
+                unsigned grp = fd_div(gm, cs.fdGHW);
+                unsigned rem = fd_mod(gm, cs.fdGHW, grp);
+                unsigned pix = rem >> cs.lgG;
+                unsigned n = (grp << cs.lgG) + (rem & ((1u << cs.lgG) - 1));
+                unsigned h = fd_div(pix, cs.fdW);
+                int wcol = fd_mod(pix, cs.fdW, h);
+                ri_nb[ci] = (long)n * cs.P;
+                ri_u[ci] = (int)h + cs.pad;
+                ri_v[ci] = wcol + cs.pad;
             } else {
                 unsigned rem = fd_div(gm, cs.fdW);
                 int wcol = fd_mod(gm, cs.fdW, rem);
@@ -243,7 +302,21 @@ void conv_gemm_body(const bf16* __restrict__ Asrc,
     };
 
     constexpr int buf = 0;
+    // TAPS: Ko % 64 == 0, so every K-tile lies inside one tap.  The mask is
+    // block-uniform (SGPRs): a tap no pixel of this tile reaches is stepped
+    // over whole, both barriers with it.  The K-tiles that remain run in the
+    // raster kernel's order, and a skipped one only added 0 * w.
+    unsigned tap_mask = 0;
+    if (TAPS)
+        tap_mask = __builtin_amdgcn_readfirstlane(dgrad_tap_mask(
+            m0, min(m0 + CBM_T, M) - 1, (int)cs.fdGHW.d, cs.lgG, cs.H, cs.W,
+            cs.P, cs.Q, cs.R, cs.S, cs.pad));
+    int tap = 0, tap_end = cs.Ko;       // [tap_end - Ko, tap_end) is tap's k
     for (int kt = 0; kt < Kgemm; kt += CBK) {
+        if (TAPS) {
+            if (kt == tap_end) { ++tap; tap_end += cs.Ko; }
+            if (!((tap_mask >> tap) & 1u)) { kt = tap_end - CBK; continue; }
+        }
         issue_tile(kt, 0);
         __syncthreads();   // vmcnt(0) for the in-flight glds + barrier
         #pragma unroll
@@ -352,7 +425,16 @@ void conv_gemm_body(const bf16* __restrict__ Asrc,
             int rl = r0_ + rsub;
             long row = (long)m0 + rl;
             int col = n0 + csub;
-            if (rl < CBM_T && row < M && col < Nout) {
+            const bool live = rl < CBM_T && row < M && col < Nout;
+            if (TAPS && live) {
+                // GEMM row -> physical dx row (n*H*W + pix)
+                unsigned gm = (unsigned)row;
+                unsigned grp = fd_div(gm, cs.fdGHW);
+                unsigned rem = fd_mod(gm, cs.fdGHW, grp);
+                unsigned n = (grp << cs.lgG) + (rem & ((1u << cs.lgG) - 1));
+                row = (long)n * (cs.H * cs.W) + (rem >> cs.lgG);
+            }
+            if (live) {
                 int i = rl * TBN + csub;    // 16 B chunk within one half
                 const bf16* src16 = i < HALF ? &stageA[i] : &stageB[i - HALF];
                 bf16x8_t v = *reinterpret_cast<const bf16x8_t*>(src16);
@@ -454,7 +536,7 @@ void conv_gemm_body(const bf16* __restrict__ Asrc,
 }
 
 template <int MODE, int TBN, int WAVES_M, int WAVES_N, bool STRIDE1 = true,
-          int CBM_T = CBM>
+          int CBM_T = CBM, bool TAPS = false>
 // min-4-waves/SIMD bound: the allocator packs the body into 122 arch
 // VGPRs (no AGPRs, zero spills) instead of 84V+64A, lifting residency
 // 3 -> 4 blocks/CU on the 128-wide tiles (and 4 -> 5 on the 64-wide) —
@@ -466,7 +548,7 @@ void k_conv_gemm(const bf16* __restrict__ Asrc, const bf16* __restrict__ Bsrc,
                  float* __restrict__ stats = nullptr,
                  BnFuse bn = BnFuse{},
                  const bf16* __restrict__ addin = nullptr) {
-    conv_gemm_body<MODE, TBN, WAVES_M, WAVES_N, STRIDE1, CBM_T>(
+    conv_gemm_body<MODE, TBN, WAVES_M, WAVES_N, STRIDE1, CBM_T, TAPS>(
         Asrc, Bsrc, bias, out, cs, M, Kgemm, Nout, stats, bn, addin);
 }
 
@@ -1578,13 +1660,84 @@ static ConvShape dgrad_shape(const at::Tensor& dy, long N, long C, long H,
     return cs;
 }
 
+struct DgradPlan {
+    const char* name;   // "raster" or "taps"
+    int G;              // taps: images per row group; raster: 0
+    long k_tiles, k_tiles_raster;   // K-tiles issued per column of M-tiles
+};
+
+// Row order of the stride-1 dgrad: every dispatch decision is made here and
+// nowhere else.  Pure host arithmetic.  group: -1 automatic, 0 raster, 32 /
+// 64 / 128 forces that G; a forced G on a shape the tap-uniform order does
+// not fit runs raster, and the plan says so.  `raster` whenever stride != 1,
+// Ko % 64 != 0 (a K-tile would straddle taps), R*S > 32 (mask bits), N % G
+// != 0, a BN slab is requested (the slab epilogue indexes raster tiles), or
+// the tap model skips nothing (1x1, valid == all).  The automatic choice is
+// MEASURED (tools/bench_kernels.py --dgradtaps, docs/KERNELS.md): a shape
+// class no measurement showed faster stays raster.
+static DgradPlan plan_dgrad(const ConvShape& cs, bool want_bn, long group) {
+    TORCH_CHECK(group == -1 || group == 0 || group == 32 || group == 64 ||
+                group == 128, "conv dgrad group must be -1 (automatic), 0 "
+                "(raster), 32, 64 or 128; got ", group);
+    const long M = (long)cs.N * cs.H * cs.W;
+    const int tiles = ceil_div_i(M, CBM);
+    DgradPlan p{"raster", 0, 0, 0};
+    p.k_tiles_raster = (long)tiles * ceil_div_i((long)cs.R * cs.S * cs.Ko, CBK);
+    p.k_tiles = p.k_tiles_raster;
+    const bool fits = cs.stride == 1 && cs.Ko % CBK == 0 &&
+                      cs.R * cs.S <= 32 && !want_bn && M < INT_MAX;
+    if (!fits || group == 0) return p;
+
+    auto count = [&](int G) {           // K-tiles the masked loop issues
+        int lg = 0;
+        while ((1 << lg) < G) ++lg;
+        // where tiles do not straddle image groups every group has the
+        // same masks: count one and multiply (this runs on every dgrad call)
+        const long ghw = (long)G * cs.H * cs.W;
+        const bool periodic = ghw % CBM == 0;
+        const int walk = periodic ? (int)(ghw / CBM) : tiles;
+        long n = 0;
+        for (int t = 0; t < walk; ++t) {
+            const int m0 = t * CBM;
+            const int m1 = (int)std::min<long>(m0 + CBM, M) - 1;
+            n += __builtin_popcount(dgrad_tap_mask(
+                m0, m1, (int)ghw, lg, cs.H, cs.W, cs.P, cs.Q, cs.R, cs.S,
+                cs.pad));
+        }
+        if (periodic) n *= cs.N / G;
+        return n * (cs.Ko / CBK);
+    };
+    // Automatic: only the shape classes the micro-benchmark showed faster
+    // by several times its spread, at the batch it ran them (B = 1024; more
+    // images only add tiles of the same kind).  Toy_Net conv3 131.7 -> 91.1
+    // us, conv4 306.8 -> 230.5 at G = 128; conv2 (179.6 -> 166.9, inside
+    // 1.3x the spread) and every shape not measured stay raster.
+    static const struct { int C, H, W, Ko, R, S, pad, G; } MEASURED[] = {
+        {128, 12, 12, 256, 3, 3, 0, 128},     // Toy_Net conv3
+        {256, 10, 10, 512, 3, 3, 0, 128},     // Toy_Net conv4
+    };
+    int G = (int)std::max<long>(group, 0);
+    if (group < 0 && cs.N >= 1024)
+        for (const auto& m : MEASURED)
+            if (cs.C == m.C && cs.H == m.H && cs.W == m.W && cs.Ko == m.Ko &&
+                cs.R == m.R && cs.S == m.S && cs.pad == m.pad)
+                G = m.G;
+    if (G == 0 || cs.N % G != 0) return p;
+    const long issued = count(G);
+    if (issued >= p.k_tiles_raster) return p;
+    p.name = "taps";
+    p.G = G;
+    p.k_tiles = issued;
+    return p;
+}
+
 // Stride-1 dgrad.  addend: optional bf16 channels_last [N,C,H,W] streamed
 // into the epilogue (dx += addend — the fused ResNet skip-grad).  bn: with
 // bn.slab set the epilogue also emits the upstream BN's backward partials.
 static at::Tensor dgrad_stride1(const at::Tensor& dy, const at::Tensor& wt2,
-                                const ConvShape& cs,
+                                ConvShape cs,
                                 const c10::optional<at::Tensor>& addend,
-                                BnFuse bn) {
+                                BnFuse bn, long group) {
     auto dx = empty_nhwc(dy, cs.N, cs.C, cs.H, cs.W);
     const bf16* adp = nullptr;
     if (addend.has_value()) {
@@ -1593,22 +1746,45 @@ static at::Tensor dgrad_stride1(const at::Tensor& dy, const at::Tensor& wt2,
         adp = reinterpret_cast<const bf16*>(addend->data_ptr());
     }
     const long M = (long)cs.N * cs.H * cs.W;
-    launch_conv_gemm<1>(at::hip::getCurrentHIPStream().stream(),
-                        ceil_div_i(M, CBM), cs.C, false,
-                        reinterpret_cast<const bf16*>(dy.data_ptr()),
-                        reinterpret_cast<const bf16*>(wt2.data_ptr()),
-                        nullptr, reinterpret_cast<bf16*>(dx.data_ptr()), cs,
-                        M, cs.R * cs.S * cs.Ko, nullptr, bn, adp);
+    const int grid_m = ceil_div_i(M, CBM);
+    const int Kgemm = cs.R * cs.S * cs.Ko;
+    auto stream = at::hip::getCurrentHIPStream().stream();
+    const bf16* dyp = reinterpret_cast<const bf16*>(dy.data_ptr());
+    const bf16* wtp = reinterpret_cast<const bf16*>(wt2.data_ptr());
+    bf16* dxp = reinterpret_cast<bf16*>(dx.data_ptr());
+    const DgradPlan plan = plan_dgrad(cs, bn.slab != nullptr, group);
+    if (plan.G == 0) {
+        launch_conv_gemm<1>(stream, grid_m, cs.C, false, dyp, wtp, nullptr,
+                            dxp, cs, M, Kgemm, nullptr, bn, adp);
+        return dx;
+    }
+    // tap-uniform row order: same tiles, grid and arguments, rows permuted
+    cs.fdGHW.init((unsigned)plan.G * cs.H * cs.W);
+    cs.lgG = 0;
+    while ((1 << cs.lgG) < plan.G) ++cs.lgG;
+    if (cs.C >= 128)
+        hipLaunchKernelGGL((k_conv_gemm<1, 128, 2, 2, true, CBM, true>),
+                           dim3(grid_m, ceil_div_i(cs.C, 128)), dim3(256), 0,
+                           stream, dyp, wtp, nullptr, dxp, cs, (int)M, Kgemm,
+                           cs.C, nullptr, BnFuse{}, adp);
+    else
+        hipLaunchKernelGGL((k_conv_gemm<1, 64, 4, 1, true, CBM, true>),
+                           dim3(grid_m, ceil_div_i(cs.C, 64)), dim3(256), 0,
+                           stream, dyp, wtp, nullptr, dxp, cs, (int)M, Kgemm,
+                           cs.C, nullptr, BnFuse{}, adp);
+    HIP_CHECK_LAST();
     return dx;
 }
 
 at::Tensor conv2d_dgrad(at::Tensor dy, at::Tensor wt2, long N, long C,
                         long H, long W, long R, long S, long stride, long pad,
-                        c10::optional<at::Tensor> addend) {
+                        c10::optional<at::Tensor> addend, long group) {
     ConvShape cs = dgrad_shape(dy, N, C, H, W, R, S, stride, pad);
     TORCH_CHECK(!addend.has_value() || cs.stride == 1,
                 "fused dgrad addend needs stride 1");
-    if (cs.stride == 1) return dgrad_stride1(dy, wt2, cs, addend, BnFuse{});
+    if (cs.stride == 1)
+        return dgrad_stride1(dy, wt2, cs, addend, BnFuse{}, group);
+    plan_dgrad(cs, false, group);       // validates group; strided is raster
 
     // NOTE: zero-stuffing dy to reach the stride-1 gather was tried and
     // REVERTED — measured slower at ResNet's strided shapes (r18 3x3/2:
@@ -1717,7 +1893,24 @@ std::vector<at::Tensor> conv2d_dgrad_bn(at::Tensor dy, at::Tensor wt2,
     bn.mean = bn_mean.data_ptr<float>();
     bn.invstd = bn_invstd.data_ptr<float>();
     bn.slab = slab.data_ptr<float>();
-    return {dgrad_stride1(dy, wt2, cs, c10::nullopt, bn), slab};
+    return {dgrad_stride1(dy, wt2, cs, c10::nullopt, bn, -1), slab};
+}
+
+// (name, G, k_tiles_issued, k_tiles_raster) conv2d_dgrad would run for this
+// shape and group argument; no tensors, launches nothing.  The counts are
+// K-tiles summed over the M-tiles of one tile column: issued is popcount of
+// each tile's tap mask times Ko/64 (the raster count when the plan is
+// raster), so a mask wider than the tile's pixels need shows up here.
+std::tuple<std::string, long, long, long> conv2d_dgrad_plan(
+        long N, long C, long H, long W, long Ko, long R, long S, long stride,
+        long pad, long group) {
+    TORCH_CHECK(N > 0 && C > 0 && Ko > 0 && R > 0 && S > 0 && stride > 0 &&
+                pad >= 0 && H + 2 * pad >= R && W + 2 * pad >= S);
+    ConvShape cs = make_shape((int)N, (int)C, (int)H, (int)W, (int)Ko, (int)R,
+                              (int)S, (int)stride, (int)pad);
+    const DgradPlan p = plan_dgrad(cs, false, group);
+    return std::make_tuple(std::string(p.name), (long)p.G, p.k_tiles,
+                           p.k_tiles_raster);
 }
 
 at::Tensor col_sum(at::Tensor x);   // gemm.hip

@@ -5,6 +5,7 @@ Usage (on a GPU box):  python tools/bench_kernels.py [--resnet]
                        python tools/bench_kernels.py --clip
                        python tools/bench_kernels.py --wgradbias
                        python tools/bench_kernels.py --wgraddma [--leaves wt3]
+                       python tools/bench_kernels.py --dgradtaps
 
 Times conv fwd/dgrad/wgrad per shape with HIP events (200 reps after 20
 warmup) and prints achieved TFLOP/s next to microseconds, so kernel A/B
@@ -404,6 +405,46 @@ def bench_wgraddma(rounds, extra, inner=10):
                 p.kill()
 
 
+def bench_dgradtaps(rounds, groups):
+    """Stride-1 dgrad of Toy_Net's conv2, conv3 and conv4 at B = 1024: the
+    raster row order (group 0) against the tap-uniform order at each G in
+    `groups`, alternated in one process (`group` is an argument, not an
+    environment variable).  Device events around 10 calls, median/min/max
+    over `rounds`; next to it the plan's K-tile count relative to raster,
+    which is what the time would be if every K-tile cost the same."""
+    ext = load_extension(required=True)
+    dev = torch.device("cuda:0")
+    print(f"{'shape':8s} {'group':>5s} {'plan':8s} {'med us':>9s} {'min':>9s} "
+          f"{'max':>9s} {'vs raster':>9s} {'model':>7s}")
+    for name, N, C, H, W, K, R, stride, pad in TOYNET[:3]:
+        P = (H + 2 * pad - R) // stride + 1
+        g = torch.Generator(device=dev).manual_seed(0)
+        dy = torch.randn(N, K, P, P, device=dev, generator=g) \
+            .to(torch.bfloat16).contiguous(memory_format=CL)
+        wt2 = torch.randn(C, R * R * K, device=dev, generator=g) \
+            .to(torch.bfloat16)
+        geo = (N, C, H, W, R, R, stride, pad)
+        variants, plans = {}, {}
+        for G in groups:
+            variants[G] = (lambda G=G: ext.conv2d_dgrad(dy, wt2, *geo,
+                                                        None, G))
+            plans[G] = ext.conv2d_dgrad_plan(N, C, H, W, K, R, R, stride,
+                                             pad, G)
+        ref = ext.conv2d_dgrad(dy, wt2, *geo, None, 0)
+        for G in groups:
+            if not torch.equal(variants[G](), ref):
+                raise RuntimeError(f"{name} group {G}: dx differs from raster")
+        res = _time_alternating(variants, rounds=rounds)
+        for G in groups:
+            med, lo, hi = res[G]
+            pname, _, issued, raster = plans[G]
+            print(f"{name:8s} {G:5d} {pname:8s} {med:9.1f} {lo:9.1f} "
+                  f"{hi:9.1f} {med / res[groups[0]][0]:9.3f} "
+                  f"{issued / raster:7.3f}", flush=True)
+        del dy, wt2, ref, variants
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clip", action="store_true")
@@ -414,6 +455,10 @@ def main():
     ap.add_argument("--leaves", default="",
                     help="further DDPX_WGRAD_V letters for --wgraddma, "
                          "comma separated (e.g. wt3)")
+    ap.add_argument("--dgradtaps", action="store_true")
+    ap.add_argument("--groups", default="0,32,64,128",
+                    help="conv2d_dgrad group values for --dgradtaps, raster "
+                         "(0) first")
     ap.add_argument("--resnet", action="store_true")
     ap.add_argument("--functional", action="store_true")
     ap.add_argument("--bn", action="store_true")
@@ -431,6 +476,10 @@ def main():
         return
     if args.wgraddma:
         bench_wgraddma(rounds=30, extra=args.leaves.split(","))
+        return
+    if args.dgradtaps:
+        bench_dgradtaps(rounds=30,
+                        groups=[int(v) for v in args.groups.split(",")])
         return
     if args.bn:
         bench_bn(args.reps)
