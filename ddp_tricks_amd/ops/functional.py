@@ -508,6 +508,154 @@ def batch_norm(x, running_mean, running_var, weight, bias,
     return y.to(x.dtype) if x.is_cuda and amp_mod.is_enabled() else y
 
 
+# -------------------------------------------------------- sync batch norm ---
+
+def _gather_rows(row, group, native):
+    from ..parallel.collectives import all_gather_rows
+    return all_gather_rows(row, group, native)
+
+
+class _HIPSyncBatchNorm(torch.autograd.Function):
+    """Training BatchNorm over the batch of every rank in ``group``.
+
+    Forward: local partial sums -> one gathered [W, 2C+2] row set ->
+    finalize + apply.  Backward: local dbeta/dgamma sums -> one gathered
+    [W, 2C] row set -> coefficients + dx.  The memory-bound passes are
+    _HIPBatchNorm's kernels; each direction adds one small launch and one
+    collective.  Every rank adds the same rows in rank order, so the saved
+    and running statistics are bitwise rank-identical.  weight/bias
+    gradients are the LOCAL sums — the DDP bucket all-reduce averages them
+    like every other parameter.  The DDPX_BNFUSE producer box is not
+    offered and DDPX_BN1PASS does not apply (both need the un-split
+    combine)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var,
+                momentum, eps, fuse_relu, residual, pre_stats, group, native):
+        ext = require_ext_for(x)
+        xb = _chlast(_to_bf16(x))
+        rb = None if residual is None else _chlast(_to_bf16(residual))
+        row = ext.bn_sync_local(xb, pre_stats)
+        gathered = _gather_rows(row, group, native)
+        y, save_mean, save_invstd, mask, count = ext.bn_sync_fwd(
+            xb, gathered, weight.detach(), bias.detach(), running_mean,
+            running_var, momentum, eps, fuse_relu, rb)
+        ctx.save_for_backward(xb, weight, save_mean, save_invstd, mask, count)
+        ctx.fuse_relu = fuse_relu
+        ctx.x_dtype = x.dtype
+        ctx.has_residual = residual is not None
+        ctx.group = group
+        ctx.native = native
+        # skip-grad fusion arming, exactly as _HIPBatchNorm
+        ctx.skip_armed = False
+        if (residual is not None and residual.is_cuda
+                and residual.dtype == torch.bfloat16 and _skipfuse_on()
+                and residual.requires_grad):
+            sb = getattr(residual, "_ddpx_skipbox", None)
+            if sb is not None:
+                ctx.skip_armed = True
+                ctx.skip_stash = sb
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xb, weight, save_mean, save_invstd, mask, count = ctx.saved_tensors
+        ext = require_ext_for(dy)
+        dyb = _chlast(_to_bf16(dy))
+        row = ext.bn_sync_bwd_local(xb, dyb, save_mean, save_invstd, mask,
+                                    ctx.fuse_relu)
+        gathered = _gather_rows(row, ctx.group, ctx.native)
+        out = ext.bn_sync_bwd_dx(xb, dyb, weight.detach(), save_mean,
+                                 save_invstd, mask, ctx.fuse_relu, gathered,
+                                 count, ctx.has_residual)
+        C = weight.numel()
+        dx, dbias, dweight = out[0], row[:C], row[C:]
+        dresid = out[1] if ctx.has_residual else None
+        if ctx.x_dtype == torch.float32:
+            dx = dx.float()
+        if dresid is not None and ctx.skip_armed:
+            stash = ctx.skip_stash
+            prev = stash.get("g")
+            stash["g"] = dresid if prev is None else prev + dresid
+            dresid = None   # delivered through the junction conv's dgrad
+        return (dx, dweight, dbias, None, None, None, None, None, dresid,
+                None, None, None)
+
+
+def _count_slots(n: int, like: torch.Tensor) -> torch.Tensor:
+    """The local row count as two exact fp32 values (n >> 12, n & 4095)."""
+    return torch.tensor([n >> 12, n & 4095], dtype=torch.float32,
+                        device=like.device)
+
+
+class _TorchSyncBatchNorm(torch.autograd.Function):
+    """Plain-torch SyncBatchNorm for CPU tensors (and GPU bring-up runs
+    without the extension): the HIP path's formulae — local sum / sumsq /
+    count rows, one gather, rank-order adds — over ``dist`` collectives."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var,
+                momentum, eps, group):
+        C = x.shape[1]
+        dims = [d for d in range(x.dim()) if d != 1]
+        n = x.numel() // C
+        row = torch.cat([x.sum(dims), (x * x).sum(dims), _count_slots(n, x)])
+        gathered = _gather_rows(row, group, None)
+        tot = gathered[0].clone()
+        for w in range(1, gathered.shape[0]):
+            tot += gathered[w]
+        M = int(tot[2 * C].item()) * 4096 + int(tot[2 * C + 1].item())
+        mean = tot[:C] / M
+        var = (tot[C:2 * C] / M - mean * mean).clamp_min(0)
+        invstd = torch.rsqrt(var + eps)
+        if running_mean is not None:
+            unbiased = var * M / (M - 1) if M > 1 else var
+            running_mean.mul_(1 - momentum).add_(momentum * mean)
+            running_var.mul_(1 - momentum).add_(momentum * unbiased)
+        shape = [1, C] + [1] * (x.dim() - 2)
+        xhat = (x - mean.view(shape)) * invstd.view(shape)
+        ctx.save_for_backward(xhat, weight, invstd)
+        ctx.M, ctx.group, ctx.dims, ctx.shape = M, group, dims, shape
+        return xhat * weight.view(shape) + bias.view(shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xhat, weight, invstd = ctx.saved_tensors
+        dims, shape, M = ctx.dims, ctx.shape, ctx.M
+        dbias = dy.sum(dims)
+        dweight = (dy * xhat).sum(dims)
+        gathered = _gather_rows(torch.cat([dbias, dweight]), ctx.group, None)
+        tot = gathered[0].clone()
+        for w in range(1, gathered.shape[0]):
+            tot += gathered[w]
+        C = weight.numel()
+        a = (weight * invstd).view(shape)
+        b = (tot[:C] / M).view(shape)
+        c = (tot[C:] / M).view(shape)
+        dx = a * (dy - b - xhat * c)
+        return dx, dweight, dbias, None, None, None, None, None
+
+
+def sync_batch_norm(x, running_mean, running_var, weight, bias, momentum,
+                    eps, group=None, native=None, fuse_relu=False,
+                    residual=None, pre_stats=None):
+    """Training-mode batch_norm whose statistics span every rank of
+    ``group`` (same epilogue fusions as ``batch_norm``).  Callers route
+    eval mode and world size 1 to ``batch_norm`` instead."""
+    if x.is_cuda and require_ext_for(x) is not None:
+        return _HIPSyncBatchNorm.apply(
+            x, weight, bias, running_mean, running_var, momentum, eps,
+            fuse_relu, residual, pre_stats, group, native)
+    xf = x.float() if x.dtype != torch.float32 else x
+    y = _TorchSyncBatchNorm.apply(xf, weight, bias, running_mean,
+                                  running_var, momentum, eps, group)
+    if residual is not None:
+        y = y + residual.float()
+    if fuse_relu:
+        y = F.relu(y)
+    return y.to(x.dtype) if x.is_cuda and amp_mod.is_enabled() else y
+
+
 class _HIPBatchNormReluPool2(torch.autograd.Function):
     """Training BatchNorm2d + fused ReLU + MaxPool2d(2) as one op.
 
@@ -552,6 +700,11 @@ def _bn_pool_fusable(bn_mod, pool_mod, x) -> bool:
     2x2/stride-2 max-pool over even extents, with no opt-in that needs the
     full-resolution activation."""
     if os.environ.get("DDPX_BNPOOL", "1") == "0":
+        return False
+    if getattr(bn_mod, "is_sync_bn", False):
+        # the junction kernels embed the un-split combine; a SyncBatchNorm
+        # runs the unfused pool(bn(conv(x))) (sync-aware junction kernels
+        # are a follow-up)
         return False
     if (os.environ.get("DDPX_BN1PASS", "0") == "1"
             or os.environ.get("DDPX_BNFUSE", "0") == "1"):

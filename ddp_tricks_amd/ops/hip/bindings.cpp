@@ -72,6 +72,21 @@ std::vector<at::Tensor> bn_fwd_train_pool2(at::Tensor x, at::Tensor gamma,
 std::vector<at::Tensor> bn_bwd_pool2(at::Tensor x, at::Tensor dy_pooled,
                                      at::Tensor gamma, at::Tensor save_mean,
                                      at::Tensor save_invstd, at::Tensor code);
+at::Tensor bn_sync_local(at::Tensor x, c10::optional<at::Tensor> pre_stats);
+std::vector<at::Tensor> bn_sync_fwd(at::Tensor x, at::Tensor gathered,
+                                    at::Tensor gamma, at::Tensor beta,
+                                    at::Tensor running_mean,
+                                    at::Tensor running_var, double momentum,
+                                    double eps, bool fuse_relu,
+                                    c10::optional<at::Tensor> residual);
+at::Tensor bn_sync_bwd_local(at::Tensor x, at::Tensor dy,
+                             at::Tensor save_mean, at::Tensor save_invstd,
+                             at::Tensor mask, bool fuse_relu);
+std::vector<at::Tensor> bn_sync_bwd_dx(at::Tensor x, at::Tensor dy,
+                                       at::Tensor gamma, at::Tensor save_mean,
+                                       at::Tensor save_invstd, at::Tensor mask,
+                                       bool fuse_relu, at::Tensor gathered,
+                                       at::Tensor count, bool want_dresid);
 
 // gemm.hip
 at::Tensor gemm_tn(at::Tensor A, at::Tensor B, c10::optional<at::Tensor> bias,
@@ -187,6 +202,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("bn_bwd_pool2", &bn_bwd_pool2,
           py::arg("x"), py::arg("dy_pooled"), py::arg("gamma"),
           py::arg("save_mean"), py::arg("save_invstd"), py::arg("code"));
+    m.def("bn_sync_local", &bn_sync_local,
+          "SyncBatchNorm forward, rank-local half: [sum | sumsq | count] row",
+          py::arg("x"), py::arg("pre_stats") = c10::nullopt);
+    m.def("bn_sync_fwd", &bn_sync_fwd,
+          "SyncBatchNorm forward, cross-rank half over gathered rows",
+          py::arg("x"), py::arg("gathered"), py::arg("gamma"),
+          py::arg("beta"), py::arg("running_mean"), py::arg("running_var"),
+          py::arg("momentum"), py::arg("eps"), py::arg("fuse_relu") = false,
+          py::arg("residual") = c10::nullopt);
+    m.def("bn_sync_bwd_local", &bn_sync_bwd_local,
+          "SyncBatchNorm backward, rank-local half: [dbeta | dgamma] row",
+          py::arg("x"), py::arg("dy"), py::arg("save_mean"),
+          py::arg("save_invstd"), py::arg("mask"),
+          py::arg("fuse_relu") = false);
+    m.def("bn_sync_bwd_dx", &bn_sync_bwd_dx,
+          "SyncBatchNorm backward, cross-rank half over gathered rows",
+          py::arg("x"), py::arg("dy"), py::arg("gamma"), py::arg("save_mean"),
+          py::arg("save_invstd"), py::arg("mask"), py::arg("fuse_relu"),
+          py::arg("gathered"), py::arg("count"),
+          py::arg("want_dresid") = false);
     m.def("gemm_tn", &gemm_tn, py::arg("A"), py::arg("B"),
           py::arg("bias") = c10::nullopt, py::arg("out_f32") = false);
     m.def("transpose_bf16", &transpose_bf16);

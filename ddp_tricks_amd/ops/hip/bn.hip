@@ -354,6 +354,117 @@ __global__ void k_bn_bwd_dx(const bf16* __restrict__ x,
     }
 }
 
+// ------------------------------------------- SyncBatchNorm split combines ---
+//
+// Cross-rank batch statistics split each combine above into a rank-local
+// half (pack: slab -> one row of per-channel sums) and a cross-rank half
+// (finalize / coefficients: add the gathered rows, then the combine's tail
+// with the GLOBAL row count).  The memory-bound passes are the kernels
+// above, unchanged.  Two properties hold by construction:
+//   * pack repeats the combine's summation order (wave per channel, lanes
+//     sweep s = lane, lane+64, ..., then wave_reduce_sum) and the cross-rank
+//     add starts from row 0, so with one rank every output is bit-identical
+//     to k_bn_combine / k_bn_bwd_combine;
+//   * every rank adds the same gathered rows in rank order w = 0..W-1, so
+//     save_mean / save_invstd / running statistics are bitwise
+//     rank-identical whatever algorithm the transport uses.
+// The local row count M rides in two fp32 slots, M >> 12 and M & 4095:
+// both are exact for M < 2^31 and survive a transport that adds zeros.
+
+constexpr int SYNC_COUNT_SHIFT = 12;
+
+// row[0:C] = per-channel sum of slab[0], row[C:2C] = of slab[1]; with
+// M >= 0 also row[2C], row[2C+1] = the split row count
+__global__ void k_bn_sync_pack(const float* __restrict__ slab, int S, int C,
+                               long M, float* __restrict__ row) {
+    int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    int lane = threadIdx.x & 63;
+    if (c >= C) return;
+    float sum = 0.f, sq = 0.f;
+    for (int s = lane; s < S; s += 64) {
+        sum += slab[(long)c * S + s];
+        sq += slab[(long)C * S + (long)c * S + s];
+    }
+    sum = wave_reduce_sum(sum);
+    sq = wave_reduce_sum(sq);
+    if (lane != 0) return;
+    row[c] = sum;
+    row[C + c] = sq;
+    if (c == 0 && M >= 0) {
+        row[2 * C] = (float)(M >> SYNC_COUNT_SHIFT);
+        row[2 * C + 1] = (float)(M & ((1l << SYNC_COUNT_SHIFT) - 1));
+    }
+}
+
+// thread per channel over gathered[W][2C+2]; k_bn_combine's tail with the
+// global M.  count (int64, device) keeps M for the backward — no host sync.
+__global__ void k_bn_sync_finalize(const float* __restrict__ gathered, int W,
+                                   int C, const float* __restrict__ gamma,
+                                   const float* __restrict__ beta,
+                                   float* __restrict__ running_mean,
+                                   float* __restrict__ running_var,
+                                   float momentum, float eps,
+                                   float* __restrict__ save_mean,
+                                   float* __restrict__ save_invstd,
+                                   float* __restrict__ scale,
+                                   float* __restrict__ shift,
+                                   long* __restrict__ count) {
+    int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const int K = 2 * C + 2;
+    float sum = gathered[c];
+    float sq = gathered[C + c];
+    long M = ((long)gathered[2 * C] << SYNC_COUNT_SHIFT)
+        + (long)gathered[2 * C + 1];
+    for (int w = 1; w < W; ++w) {
+        const float* g = gathered + (long)w * K;
+        sum += g[c];
+        sq += g[C + c];
+        M += ((long)g[2 * C] << SYNC_COUNT_SHIFT) + (long)g[2 * C + 1];
+    }
+    if (c == 0) count[0] = M;
+    float mean = sum / M;
+    float var = fmaxf(sq / M - mean * mean, 0.f);
+    float invstd = rsqrtf(var + eps);
+    save_mean[c] = mean;
+    save_invstd[c] = invstd;
+    float g = gamma ? gamma[c] : 1.f;
+    float b = beta ? beta[c] : 0.f;
+    float sc = g * invstd;
+    scale[c] = sc;
+    shift[c] = b - mean * sc;
+    if (running_mean) {
+        float unbiased = M > 1 ? var * M / (M - 1) : var;
+        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean;
+        running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
+    }
+}
+
+// thread per channel over gathered[W][2C] (dbeta | dgamma rows);
+// k_bn_bwd_combine's coefficients with the global count
+__global__ void k_bn_sync_bwd_coef(const float* __restrict__ gathered, int W,
+                                   int C, const long* __restrict__ count,
+                                   const float* __restrict__ gamma,
+                                   const float* __restrict__ save_invstd,
+                                   float* __restrict__ coef_a,
+                                   float* __restrict__ coef_b,
+                                   float* __restrict__ coef_c) {
+    int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const int K = 2 * C;
+    float sum_dy = gathered[c];
+    float sum_dyx = gathered[C + c];
+    for (int w = 1; w < W; ++w) {
+        sum_dy += gathered[(long)w * K + c];
+        sum_dyx += gathered[(long)w * K + C + c];
+    }
+    long M = count[0];
+    float g = gamma ? gamma[c] : 1.f;
+    coef_a[c] = g * save_invstd[c];
+    coef_b[c] = sum_dy / M;
+    coef_c[c] = sum_dyx / M;
+}
+
 // ------------------------------------ BN + ReLU + 2x2/s2 max-pool, fused ---
 //
 // At a BatchNorm(fuse_relu) -> MaxPool2d(2) junction the full-resolution
@@ -1026,6 +1137,242 @@ std::vector<at::Tensor> bn_bwd(at::Tensor x, at::Tensor dy, at::Tensor gamma,
     HIP_CHECK_LAST();
     if (want_dresid) return {dx, dgamma, dbeta, dresid};
     return {dx, dgamma, dbeta};
+}
+
+// ------------------------------------------------- SyncBatchNorm hosts -----
+
+static void check_sync_input(const at::Tensor& x, const char* who) {
+    TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16, who,
+                " needs a bf16 device input");
+    TORCH_CHECK(x.dim() == 2 ? x.is_contiguous()
+                : x.dim() == 4
+                  && x.is_contiguous(at::MemoryFormat::ChannelsLast),
+                who, " needs a contiguous 2-d or channels_last 4-d input");
+}
+
+static void check_sync_vec(const at::Tensor& t, long n, const char* who,
+                           const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat
+                && t.is_contiguous() && t.numel() == n,
+                who, ": ", name, " must be contiguous fp32 with ", n,
+                " elements");
+}
+
+static void check_sync_gathered(const at::Tensor& g, long K, const char* who) {
+    TORCH_CHECK(g.is_cuda() && g.scalar_type() == at::kFloat && g.dim() == 2
+                && g.is_contiguous() && g.size(0) >= 1 && g.size(1) == K,
+                who, " needs contiguous fp32 gathered rows [W, ", K, "]");
+}
+
+// Rank-local half of the forward: the statistics pass (skipped with
+// pre_stats) and the pack.  row = [sum(C) | sumsq(C) | M >> 12 | M & 4095].
+at::Tensor bn_sync_local(at::Tensor x, c10::optional<at::Tensor> pre_stats) {
+    check_sync_input(x, "bn_sync_local");
+    long M; int C;
+    shape_mc(x, M, C);
+    TORCH_CHECK(C % 8 == 0 && C / 8 <= 256, "bn HIP path needs C%8==0");
+    TORCH_CHECK(M >= 1 && M < (1l << 31), "bn_sync_local: row count ", M);
+    auto stream = at::hip::getCurrentHIPStream();
+    auto fopts = x.options().dtype(at::kFloat);
+    int block = pick_block(C);
+    int nw = block / (C / 8);
+    if (pre_stats.has_value())
+        TORCH_CHECK(pre_stats->is_cuda() && pre_stats->dim() == 3
+                    && pre_stats->scalar_type() == at::kFloat
+                    && pre_stats->is_contiguous() && pre_stats->size(0) == 2
+                    && pre_stats->size(1) == C && pre_stats->size(2) >= 1,
+                    "bn_sync_local: pre_stats must be fp32 [2, C, S]");
+    int S = pre_stats.has_value() ? (int)pre_stats->size(2)
+                                  : bn_splits(M, nw);
+    auto slab = pre_stats.has_value() ? *pre_stats
+                                      : at::empty({2, C, S}, fopts);
+    auto row = at::empty({2 * (long)C + 2}, fopts);
+    if (!pre_stats.has_value()) {
+        hipLaunchKernelGGL(k_bn_partial, dim3(S), dim3(block), 2 * nw * C * 4,
+                           stream.stream(),
+                           reinterpret_cast<const bf16*>(x.data_ptr()), M, C,
+                           S, slab.data_ptr<float>());
+        HIP_CHECK_LAST();
+    }
+    hipLaunchKernelGGL(k_bn_sync_pack, dim3(ceil_div_i(C, 4)), dim3(256), 0,
+                       stream.stream(), slab.data_ptr<float>(), S, C, M,
+                       row.data_ptr<float>());
+    HIP_CHECK_LAST();
+    return row;
+}
+
+// Cross-rank half of the forward: finalize over the gathered rows, then
+// the unchanged apply.  Returns {y, save_mean, save_invstd, mask, count}.
+std::vector<at::Tensor> bn_sync_fwd(at::Tensor x, at::Tensor gathered,
+                                    at::Tensor gamma, at::Tensor beta,
+                                    at::Tensor running_mean,
+                                    at::Tensor running_var, double momentum,
+                                    double eps, bool fuse_relu,
+                                    c10::optional<at::Tensor> residual) {
+    check_sync_input(x, "bn_sync_fwd");
+    long M; int C;
+    shape_mc(x, M, C);
+    TORCH_CHECK(C % 8 == 0 && C / 8 <= 256, "bn HIP path needs C%8==0");
+    check_sync_gathered(gathered, 2 * (long)C + 2, "bn_sync_fwd");
+    check_sync_vec(gamma, C, "bn_sync_fwd", "gamma");
+    check_sync_vec(beta, C, "bn_sync_fwd", "beta");
+    check_sync_vec(running_mean, C, "bn_sync_fwd", "running_mean");
+    check_sync_vec(running_var, C, "bn_sync_fwd", "running_var");
+    if (residual.has_value()) {
+        check_sync_input(*residual, "bn_sync_fwd residual");
+        TORCH_CHECK(residual->sizes() == x.sizes(),
+                    "bn_sync_fwd: residual shape differs from x");
+    }
+    auto stream = at::hip::getCurrentHIPStream();
+    auto fopts = gamma.options().dtype(at::kFloat);
+    auto save_mean = at::empty({C}, fopts);
+    auto save_invstd = at::empty({C}, fopts);
+    auto scale = at::empty({C}, fopts);
+    auto shift = at::empty({C}, fopts);
+    auto count = at::empty({1}, gamma.options().dtype(at::kLong));
+    auto y = x.dim() == 4
+        ? at::empty_like(x, x.options().memory_format(at::MemoryFormat::ChannelsLast))
+        : at::empty_like(x);
+    hipLaunchKernelGGL(k_bn_sync_finalize, dim3(ceil_div_i(C, 64)), dim3(64),
+                       0, stream.stream(), gathered.data_ptr<float>(),
+                       (int)gathered.size(0), C, gamma.data_ptr<float>(),
+                       beta.data_ptr<float>(),
+                       running_mean.data_ptr<float>(),
+                       running_var.data_ptr<float>(),
+                       (float)momentum, (float)eps,
+                       save_mean.data_ptr<float>(),
+                       save_invstd.data_ptr<float>(),
+                       scale.data_ptr<float>(), shift.data_ptr<float>(),
+                       reinterpret_cast<long*>(count.data_ptr<int64_t>()));
+    HIP_CHECK_LAST();
+    long tv = M * C / 8;
+    int blocks = std::min<long>(4096, ceil_div_i(tv, 256));
+    const bf16* rp = residual.has_value()
+        ? reinterpret_cast<const bf16*>(residual->data_ptr()) : nullptr;
+    at::Tensor mask;
+    unsigned char* mp = nullptr;
+    if (fuse_relu) {
+        mask = at::empty({M, C / 8}, x.options().dtype(at::kByte));
+        mp = mask.data_ptr<unsigned char>();
+    } else {
+        mask = at::empty({0}, x.options().dtype(at::kByte));
+    }
+    hipLaunchKernelGGL(k_bn_apply_v8, dim3(blocks), dim3(256), 0,
+                       stream.stream(),
+                       reinterpret_cast<const bf16*>(x.data_ptr()),
+                       reinterpret_cast<bf16*>(y.data_ptr()),
+                       scale.data_ptr<float>(), shift.data_ptr<float>(), tv,
+                       C / 8, fuse_relu, rp, mp);
+    HIP_CHECK_LAST();
+    return {y, save_mean, save_invstd, mask, count};
+}
+
+static void check_sync_bwd(const at::Tensor& x, const at::Tensor& dy,
+                           const at::Tensor& save_mean,
+                           const at::Tensor& save_invstd,
+                           const at::Tensor& mask, bool fuse_relu, long M,
+                           int C, const char* who) {
+    check_sync_input(x, who);
+    check_sync_input(dy, who);
+    TORCH_CHECK(dy.sizes() == x.sizes(), who, ": dy shape differs from x");
+    TORCH_CHECK(C % 8 == 0 && C / 8 <= 256, "bn HIP path needs C%8==0");
+    check_sync_vec(save_mean, C, who, "save_mean");
+    check_sync_vec(save_invstd, C, who, "save_invstd");
+    TORCH_CHECK(!fuse_relu
+                || (mask.is_cuda() && mask.scalar_type() == at::kByte
+                    && mask.is_contiguous() && mask.numel() == M * (C / 8)),
+                who, " needs the packed relu mask from bn_sync_fwd");
+}
+
+// Rank-local half of the backward: row = [dbeta(C) | dgamma(C)], the local
+// sums (the parameter gradients; the DDP all-reduce averages them).
+at::Tensor bn_sync_bwd_local(at::Tensor x, at::Tensor dy,
+                             at::Tensor save_mean, at::Tensor save_invstd,
+                             at::Tensor mask, bool fuse_relu) {
+    long M; int C;
+    shape_mc(x, M, C);
+    check_sync_bwd(x, dy, save_mean, save_invstd, mask, fuse_relu, M, C,
+                   "bn_sync_bwd_local");
+    auto stream = at::hip::getCurrentHIPStream();
+    auto fopts = save_mean.options();
+    int block = pick_block(C);
+    int nw = block / (C / 8);
+    int S = bn_splits(M, nw);
+    auto slab = at::empty({2, C, S}, fopts);
+    auto row = at::empty({2 * (long)C}, fopts);
+    hipLaunchKernelGGL(k_bn_bwd_partial, dim3(S), dim3(block), 2 * nw * C * 4,
+                       stream.stream(),
+                       reinterpret_cast<const bf16*>(x.data_ptr()),
+                       reinterpret_cast<const bf16*>(dy.data_ptr()),
+                       fuse_relu ? mask.data_ptr<unsigned char>() : nullptr,
+                       save_mean.data_ptr<float>(),
+                       save_invstd.data_ptr<float>(), M, C, S, fuse_relu,
+                       slab.data_ptr<float>());
+    HIP_CHECK_LAST();
+    hipLaunchKernelGGL(k_bn_sync_pack, dim3(ceil_div_i(C, 4)), dim3(256), 0,
+                       stream.stream(), slab.data_ptr<float>(), S, C, -1l,
+                       row.data_ptr<float>());
+    HIP_CHECK_LAST();
+    return row;
+}
+
+// Cross-rank half of the backward: coefficients from the gathered rows and
+// the forward's global count, then the unchanged dx pass.
+std::vector<at::Tensor> bn_sync_bwd_dx(at::Tensor x, at::Tensor dy,
+                                       at::Tensor gamma, at::Tensor save_mean,
+                                       at::Tensor save_invstd, at::Tensor mask,
+                                       bool fuse_relu, at::Tensor gathered,
+                                       at::Tensor count, bool want_dresid) {
+    long M; int C;
+    shape_mc(x, M, C);
+    check_sync_bwd(x, dy, save_mean, save_invstd, mask, fuse_relu, M, C,
+                   "bn_sync_bwd_dx");
+    check_sync_vec(gamma, C, "bn_sync_bwd_dx", "gamma");
+    check_sync_gathered(gathered, 2 * (long)C, "bn_sync_bwd_dx");
+    TORCH_CHECK(count.is_cuda() && count.scalar_type() == at::kLong
+                && count.numel() == 1,
+                "bn_sync_bwd_dx needs the int64 count from bn_sync_fwd");
+    auto stream = at::hip::getCurrentHIPStream();
+    auto fopts = gamma.options().dtype(at::kFloat);
+    int block = pick_block(C);
+    int nw = block / (C / 8);
+    auto ca = at::empty({C}, fopts);
+    auto cb = at::empty({C}, fopts);
+    auto cc = at::empty({C}, fopts);
+    auto dx = x.dim() == 4
+        ? at::empty_like(x, x.options().memory_format(at::MemoryFormat::ChannelsLast))
+        : at::empty_like(x);
+    hipLaunchKernelGGL(k_bn_sync_bwd_coef, dim3(ceil_div_i(C, 64)), dim3(64),
+                       0, stream.stream(), gathered.data_ptr<float>(),
+                       (int)gathered.size(0), C,
+                       reinterpret_cast<const long*>(
+                           count.data_ptr<int64_t>()),
+                       gamma.data_ptr<float>(), save_invstd.data_ptr<float>(),
+                       ca.data_ptr<float>(), cb.data_ptr<float>(),
+                       cc.data_ptr<float>());
+    HIP_CHECK_LAST();
+    at::Tensor dresid;
+    bf16* drp = nullptr;
+    if (want_dresid) {
+        dresid = x.dim() == 4
+            ? at::empty_like(x, x.options().memory_format(at::MemoryFormat::ChannelsLast))
+            : at::empty_like(x);
+        drp = reinterpret_cast<bf16*>(dresid.data_ptr());
+    }
+    int dxblocks = (int)std::max<long>(1, std::min<long>(2048, M / (nw * 2)));
+    hipLaunchKernelGGL(k_bn_bwd_dx, dim3(dxblocks), dim3(block), 0,
+                       stream.stream(),
+                       reinterpret_cast<const bf16*>(x.data_ptr()),
+                       reinterpret_cast<const bf16*>(dy.data_ptr()),
+                       fuse_relu ? mask.data_ptr<unsigned char>() : nullptr,
+                       save_mean.data_ptr<float>(),
+                       save_invstd.data_ptr<float>(), ca.data_ptr<float>(),
+                       cb.data_ptr<float>(), cc.data_ptr<float>(),
+                       reinterpret_cast<bf16*>(dx.data_ptr()), M, C,
+                       fuse_relu, drp);
+    HIP_CHECK_LAST();
+    if (want_dresid) return {dx, dresid};
+    return {dx};
 }
 
 // ---------------------------------------------- BN + ReLU + pool2 hosts ----

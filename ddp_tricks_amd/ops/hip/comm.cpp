@@ -80,6 +80,22 @@ void rccl_broadcast(at::Tensor t, int64_t root, int64_t handle) {
                              stream.stream()));
 }
 
+// dst[W, ...] <- every rank's src, in rank order (SyncBatchNorm's per-layer
+// statistics rows: every rank then reduces identical bytes in one order)
+void rccl_all_gather(at::Tensor src, at::Tensor dst, int64_t handle) {
+    TORCH_CHECK(src.is_cuda() && src.is_contiguous() && dst.is_cuda()
+                && dst.is_contiguous()
+                && src.scalar_type() == dst.scalar_type());
+    ncclComm_t comm = get_comm(handle);
+    int nranks = 0;
+    RCCL_CHECK(ncclCommCount(comm, &nranks));
+    TORCH_CHECK(dst.numel() == src.numel() * nranks,
+                "rccl_all_gather: dst must hold one src per rank");
+    auto stream = at::hip::getCurrentHIPStream();
+    RCCL_CHECK(ncclAllGather(src.data_ptr(), dst.data_ptr(), src.numel(),
+                             nccl_dtype(src), comm, stream.stream()));
+}
+
 void rccl_group_start() { RCCL_CHECK(ncclGroupStart()); }
 void rccl_group_end() { RCCL_CHECK(ncclGroupEnd()); }
 
@@ -99,6 +115,8 @@ void register_comm(py::module_& m) {
     m.def("rccl_all_reduce", &rccl_all_reduce,
           py::arg("t"), py::arg("handle"), py::arg("avg") = false);
     m.def("rccl_broadcast", &rccl_broadcast);
+    m.def("rccl_all_gather", &rccl_all_gather,
+          py::arg("src"), py::arg("dst"), py::arg("handle"));
     m.def("rccl_group_start", &rccl_group_start);
     m.def("rccl_group_end", &rccl_group_end);
     m.def("rccl_comm_destroy", &rccl_comm_destroy);

@@ -62,6 +62,53 @@ class BatchNorm1d(nn.BatchNorm1d, _BatchNormBase):
         return self._bn_forward(x)
 
 
+class SyncBatchNorm(nn.modules.batchnorm._BatchNorm, _BatchNormBase):
+    """BatchNorm whose training statistics span every rank of
+    ``process_group`` (2-D and 4-D input).
+
+    Parameters, buffers and state_dict keys are BatchNorm1d/2d's, so
+    checkpoints are interchangeable.  With world size 1, or no initialised
+    process group, and in eval mode, forward IS the plain ``batch_norm``
+    path: no collective, no extra kernel.  The DDP wrapper hands its
+    native RCCL communicator (or none) to ``_native_comm`` so every rank
+    takes the same transport."""
+
+    is_sync_bn = True
+
+    def __init__(self, *args, fuse_relu: bool = False, process_group=None,
+                 **kwargs):
+        super().__init__(*args, **kwargs)
+        if not (self.affine and self.track_running_stats):
+            raise ValueError("SyncBatchNorm needs affine=True and "
+                             "track_running_stats=True")
+        self.fuse_relu = fuse_relu
+        self.process_group = process_group
+        self._native_comm = None
+
+    def _check_input_dim(self, x):
+        if x.dim() not in (2, 4):
+            raise ValueError(f"expected 2D or 4D input (got {x.dim()}D input)")
+
+    def _world(self) -> int:
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            return 1
+        return dist.get_world_size(self.process_group)
+
+    def forward(self, x, residual=None, pre_stats=None):
+        if not self.training or self._world() == 1:
+            return self._bn_forward(x, residual, pre_stats)
+        self._check_input_dim(x)
+        if self.num_batches_tracked is not None:
+            self.num_batches_tracked.add_(1)
+        momentum = self.momentum if self.momentum is not None else 0.1
+        return F_ops.sync_batch_norm(
+            x, self.running_mean, self.running_var, self.weight, self.bias,
+            momentum, self.eps, group=self.process_group,
+            native=self._native_comm, fuse_relu=self.fuse_relu,
+            residual=residual, pre_stats=pre_stats)
+
+
 class ReLU(nn.ReLU):
     def forward(self, x):
         return F_ops.relu(x, inplace=self.inplace)

@@ -114,6 +114,14 @@ class DistributedDataParallel(nn.Module):
                             f"native RCCL init failed ({err}); falling back "
                             "to the torch process-group collectives")
 
+        # SyncBatchNorm layers gather their statistics rows over the same
+        # transport decision the ranks just agreed on: the native
+        # communicator when it engaged, the process group otherwise
+        for m in module.modules():
+            if getattr(m, "is_sync_bn", False) \
+                    and m.process_group is self.process_group:
+                m._native_comm = self._rccl
+
         if self.world_size > 1:
             self._broadcast_params()
         self._coalesce_buffers()

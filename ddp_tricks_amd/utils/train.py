@@ -140,6 +140,11 @@ def train(args):
     same_seeds(args.seed_num)
     model = build_model(model_name, **model_kwargs)
     model = model.to(device)
+    if getattr(args, "sync_bn", False):
+        # opt-in cross-rank BatchNorm statistics; parameters and buffers
+        # stay the same objects, so everything below is unaffected
+        from ..parallel.sync_bn import convert_sync_batchnorm
+        model = convert_sync_batchnorm(model)
 
     os.makedirs(os.path.join(args.model_path, "logs"), exist_ok=True)
     latest_model_path = os.path.join(args.model_path, args.exp_name)

@@ -61,6 +61,10 @@ def parse_args():
     parser.add_argument("--normalize", action="store_true",
                         help="normalise train and valid images with the "
                              "dataset's per-channel MEAN/STD")
+    parser.add_argument("--sync_bn", action="store_true",
+                        help="convert every BatchNorm to SyncBatchNorm: "
+                             "batch statistics over all ranks, one small "
+                             "gather per layer and direction")
     args = parser.parse_args()
     if args.local_rank is None:
         args.local_rank = int(os.environ.get("LOCAL_RANK", 0))
