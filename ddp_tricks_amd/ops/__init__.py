@@ -111,6 +111,6 @@ def require_ext_for(tensor):
 
 from .functional import (  # noqa: E402,F401
     conv2d, linear, batch_norm, max_pool2d, relu, cross_entropy_loss,
-    clip_grad_norm_, sync_batch_norm,
+    clip_grad_norm_, sync_batch_norm, MixedTarget,
 )
 from .optim import FusedSGD  # noqa: E402,F401

@@ -867,12 +867,103 @@ class _HIPCrossEntropy(torch.autograd.Function):
         return dlogits, None
 
 
-def cross_entropy_loss(logits, target):
+class MixedTarget:
+    """A target pair with a per-row weight: row i is class ``a[i]`` with
+    weight ``lam[i]`` and class ``b[i]`` with weight ``1 - lam[i]`` (CutMix,
+    or a mixup of the caller's own).  ``a``/``b`` int64 [B], ``lam`` fp32 [B]."""
+
+    __slots__ = ("a", "b", "lam")
+
+    def __init__(self, a, b, lam):
+        self.a, self.b, self.lam = a, b, lam
+
+    def to(self, device=None, non_blocking: bool = False):
+        kw = dict(device=device, non_blocking=non_blocking)
+        return MixedTarget(self.a.to(dtype=torch.long, **kw),
+                           self.b.to(dtype=torch.long, **kw),
+                           self.lam.to(dtype=torch.float32, **kw))
+
+    def dominant(self) -> torch.Tensor:
+        """The class that carries at least half of the weight (accuracy is
+        counted against it)."""
+        return torch.where(self.lam >= 0.5, self.a, self.b)
+
+    def __len__(self):
+        return self.a.shape[0]
+
+    def __repr__(self):
+        return f"MixedTarget(a={self.a}, b={self.b}, lam={self.lam})"
+
+
+class _HIPMixCrossEntropy(torch.autograd.Function):
+    """CE against q = eps/C + (1-eps)(lam*onehot(a) + (1-lam)*onehot(b));
+    no gradient to the targets or to lam."""
+
+    @staticmethod
+    def forward(ctx, logits, a, b, lam, smoothing):
+        ext = require_ext_for(logits)
+        lb = logits.contiguous()
+        loss, lse = ext.ce_mix_fwd(lb, a, b, lam, smoothing)
+        ctx.save_for_backward(lb, a, b, lam, lse)
+        ctx.smoothing = smoothing
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        logits, a, b, lam, lse = ctx.saved_tensors
+        ext = require_ext_for(logits)
+        dlogits = ext.ce_mix_bwd(logits, a, b, lam, lse, dloss.contiguous(),
+                                 ctx.smoothing)
+        return dlogits, None, None, None, None
+
+
+_ONES_CACHE: dict = {}
+
+
+def _ones_f32(n: int, device) -> torch.Tensor:
+    """Cached all-ones fp32 [n] (lam of a hard target); never written."""
+    key = (n, device)
+    t = _ONES_CACHE.get(key)
+    if t is None:
+        if len(_ONES_CACHE) >= 16:
+            _ONES_CACHE.clear()
+        t = _ONES_CACHE[key] = torch.ones(n, dtype=torch.float32,
+                                          device=device)
+    return t
+
+
+def cross_entropy_loss(logits, target, label_smoothing: float = 0.0):
     """Mean-reduced CE (the engine applies the reference's extra /B on top —
-    reference utils/process.py:22-23)."""
+    reference utils/process.py:22-23).
+
+    ``target`` is an int64 class tensor or a ``MixedTarget``; with
+    ``label_smoothing`` = eps the target distribution of row i is
+    ``eps/C + (1-eps)*(lam_i*onehot(a_i) + (1-lam_i)*onehot(b_i))``.  A
+    tensor target without smoothing takes the plain hard-target kernels."""
+    eps = float(label_smoothing)
+    mixed = isinstance(target, MixedTarget)
+    if not mixed and eps == 0.0:
+        if logits.is_cuda and require_ext_for(logits) is not None:
+            return _HIPCrossEntropy.apply(logits, target)
+        return F.cross_entropy(logits.float(), target)
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1), got {eps}")
+    if mixed:
+        a, b, lam = target.a, target.b, target.lam
+    else:
+        a = b = target
+        lam = None
     if logits.is_cuda and require_ext_for(logits) is not None:
-        return _HIPCrossEntropy.apply(logits, target)
-    return F.cross_entropy(logits.float(), target)
+        if lam is None:
+            lam = _ones_f32(logits.shape[0], logits.device)
+        return _HIPMixCrossEntropy.apply(logits, a, b, lam, eps)
+    x = logits.float()
+    ce_a = F.cross_entropy(x, a, reduction="none", label_smoothing=eps)
+    if lam is None:
+        return ce_a.mean()
+    ce_b = F.cross_entropy(x, b, reduction="none", label_smoothing=eps)
+    lam = lam.to(torch.float32)
+    return (lam * ce_a + (1.0 - lam) * ce_b).mean()
 
 
 def argmax_correct(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:

@@ -30,6 +30,12 @@ std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor target);
 at::Tensor ce_bwd(at::Tensor logits, at::Tensor target, at::Tensor lse,
                   at::Tensor dloss);
 at::Tensor argmax_correct(at::Tensor logits, at::Tensor target);
+std::vector<at::Tensor> ce_mix_fwd(at::Tensor logits, at::Tensor target_a,
+                                   at::Tensor target_b, at::Tensor lam,
+                                   double smoothing);
+at::Tensor ce_mix_bwd(at::Tensor logits, at::Tensor target_a,
+                      at::Tensor target_b, at::Tensor lam, at::Tensor lse,
+                      at::Tensor dloss, double smoothing);
 
 // pool.hip
 std::vector<at::Tensor> maxpool2x2_fwd(at::Tensor x);
@@ -129,6 +135,10 @@ std::vector<at::Tensor> batch_gather_aug(at::Tensor store, at::Tensor labels,
                                          at::Tensor index, at::Tensor lut,
                                          long pad, bool hflip, long seed,
                                          long epoch);
+std::vector<at::Tensor> batch_gather_cutmix(at::Tensor store, at::Tensor labels,
+                                            at::Tensor index, at::Tensor lut,
+                                            long pad, bool hflip, long seed,
+                                            long epoch, long prob_thresh);
 
 // comm.cpp
 void register_comm(py::module_& m);
@@ -169,6 +179,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("ce_fwd", &ce_fwd);
     m.def("ce_bwd", &ce_bwd);
     m.def("argmax_correct", &argmax_correct);
+    m.def("ce_mix_fwd", &ce_mix_fwd,
+          "CE against q = eps/C + (1-eps)(lam*onehot(a) + (1-lam)*onehot(b)): "
+          "(mean loss, lse)",
+          py::arg("logits"), py::arg("target_a"), py::arg("target_b"),
+          py::arg("lam"), py::arg("smoothing"));
+    m.def("ce_mix_bwd", &ce_mix_bwd,
+          py::arg("logits"), py::arg("target_a"), py::arg("target_b"),
+          py::arg("lam"), py::arg("lse"), py::arg("dloss"),
+          py::arg("smoothing"));
     m.def("maxpool2x2_fwd", &maxpool2x2_fwd);
     m.def("maxpool2x2_bwd", &maxpool2x2_bwd);
     m.def("maxpool_fwd", &maxpool_fwd);
@@ -263,4 +282,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("store"), py::arg("labels"), py::arg("index"),
           py::arg("lut"), py::arg("pad"), py::arg("hflip"), py::arg("seed"),
           py::arg("epoch"));
+    m.def("batch_gather_cutmix", &batch_gather_cutmix,
+          "batch_gather_aug with CutMix: (images, labels_a, labels_b, lam); "
+          "prob_thresh is the apply probability in 1/65536",
+          py::arg("store"), py::arg("labels"), py::arg("index"),
+          py::arg("lut"), py::arg("pad"), py::arg("hflip"), py::arg("seed"),
+          py::arg("epoch"), py::arg("prob_thresh"));
 }

@@ -16,10 +16,13 @@ torchvision and without network access:
   * ``DeviceBatchLoader`` (opt-in) keeps the dataset on the GPU as uint8 and
     builds each batch — gather, crop, flip, normalise, bf16 channels_last —
     with one HIP kernel launch (``ops/hip/data.hip``); on CPU it is the
-    reference implementation of the same augmentation.
+    reference implementation of the same augmentation.  With
+    ``Augment(cutmix_prob=...)`` the same launch also pastes a hashed box of
+    a partner sample (CutMix) and the batches carry ``MixedTarget`` labels.
 """
 from __future__ import annotations
 
+import collections
 import gzip
 import math
 import os
@@ -465,6 +468,73 @@ def sample_params(seed: int, epoch: int, index, pad: int, hflip: bool):
     return dx.astype(np.int64), dy.astype(np.int64), flip.astype(np.int64)
 
 
+def _mix_hash(seed: int, epoch: int, idx: np.ndarray) -> np.ndarray:
+    u = np.uint64
+    s = np.full(1, int(seed) & _U64, dtype=np.uint64)
+    e = np.full(1, int(epoch), dtype=np.uint64)
+    key = (e << u(32)) | idx
+    z = s + (key + u(1)) * u(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> u(30))) * u(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> u(27))) * u(0x94D049BB133111EB)
+    return z ^ (z >> u(31))
+
+
+# seed offsets of the two CutMix hashes (ops/hip/data.hip, file header)
+MIX_SEED_A = 0xD1B54A32D192ED03
+MIX_SEED_B = 0x8CB92BA72F3D8DD7
+
+
+def cutmix_threshold(prob: float) -> int:
+    """Apply probability as the kernel's 16-bit threshold: a sample is mixed
+    when its 16 hashed bits are below ``floor(prob * 65536 + 0.5)``."""
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError(f"cutmix_prob must be in [0, 1], got {prob}")
+    return int(math.floor(float(prob) * 65536.0 + 0.5))
+
+
+CutMixParams = collections.namedtuple(
+    "CutMixParams", "j apply box area lam raw")
+
+
+def cutmix_params(seed: int, epoch: int, index, N: int, H: int, W: int,
+                  prob: float) -> CutMixParams:
+    """Per-sample CutMix parameters — the numpy mirror of ``mix_decode`` in
+    ``ops/hip/data.hip`` (integers only, layout in that file's header).
+    Keyed by (seed, epoch, DATASET index) like ``sample_params``.
+
+    Returns int64 arrays: partner ``j`` in [0, N), ``apply`` (0/1), ``box``
+    = (x0, y0, x1, y1) half-open and clipped to the image, ``area`` of the
+    clipped box; ``lam`` float32 = (HW - area)/HW, 1 where not applied; and
+    ``raw`` = (cx, cy, bw, bh), the centre and the unclipped box size.  The
+    box and area are reported whether or not the sample is applied."""
+    idx = np.atleast_1d(np.asarray(index)).astype(np.uint64)
+    u = np.uint64
+    z2 = _mix_hash(int(seed) + MIX_SEED_A, epoch, idx)
+    z3 = _mix_hash(int(seed) + MIX_SEED_B, epoch, idx)
+    j = ((z2 & u(0xFFFFFFFF)) * u(N)) >> u(32)
+    v = (z2 >> u(32)).astype(np.int64)
+    r = np.floor(np.sqrt(v.astype(np.float64))).astype(np.int64)
+    r = np.where(r * r > v, r - 1, r)                 # exact floor sqrt
+    r = np.where((r + 1) * (r + 1) <= v, r + 1, r)
+    cx = (((z3 & u(0xFFFF)) * u(W)) >> u(16)).astype(np.int64)
+    cy = ((((z3 >> u(16)) & u(0xFFFF)) * u(H)) >> u(16)).astype(np.int64)
+    bits = ((z3 >> u(32)) & u(0xFFFF)).astype(np.int64)
+    apply = (bits < cutmix_threshold(prob)).astype(np.int64)
+    bw = (r * W) >> 16
+    bh = (r * H) >> 16
+    x0 = cx - bw // 2
+    y0 = cy - bh // 2
+    x1 = np.minimum(x0 + bw, W)
+    y1 = np.minimum(y0 + bh, H)
+    x0 = np.maximum(x0, 0)
+    y0 = np.maximum(y0, 0)
+    area = (x1 - x0) * (y1 - y0)
+    hw = np.float32(H * W)
+    lam = ((H * W - area * apply).astype(np.float32) / hw).astype(np.float32)
+    return CutMixParams(j.astype(np.int64), apply, (x0, y0, x1, y1), area,
+                        lam, (cx, cy, bw, bh))
+
+
 class Augment:
     """Augmentation / normalisation config of ``DeviceBatchLoader``.
 
@@ -472,12 +542,17 @@ class Augment:
     zero-padded by P pixels (torchvision ``RandomCrop(padding=P)``);
     ``hflip``: random horizontal flip; ``mean``/``std``: per-channel
     normalisation.  The kernel does no arithmetic on pixels — everything
-    value-related is folded into the ``[C, 256]`` bf16 table of ``lut()``."""
+    value-related is folded into the ``[C, 256]`` bf16 table of ``lut()``.
+    ``cutmix_prob`` > 0 pastes, with that probability per sample, a hashed
+    box of a partner sample (``cutmix_params``) and makes the loader yield
+    ``MixedTarget`` labels."""
 
     def __init__(self, crop_pad: int = 0, hflip: bool = False,
-                 mean=None, std=None):
+                 mean=None, std=None, cutmix_prob: float = 0.0):
         if crop_pad < 0:
             raise ValueError("crop_pad must be >= 0")
+        self.cutmix_prob = float(cutmix_prob)
+        cutmix_threshold(self.cutmix_prob)       # range check
         if (mean is None) != (std is None):
             raise ValueError("mean and std go together")
         self.crop_pad = int(crop_pad)
@@ -502,8 +577,9 @@ class Augment:
         return t.to(torch.bfloat16).contiguous()
 
     def __repr__(self):
+        mix = f", cutmix_prob={self.cutmix_prob}" if self.cutmix_prob else ""
         return (f"Augment(crop_pad={self.crop_pad}, hflip={self.hflip}, "
-                f"mean={self.mean}, std={self.std})")
+                f"mean={self.mean}, std={self.std}{mix})")
 
 
 def quantize_store(images: torch.Tensor, chunk: int = 1024) -> torch.Tensor:
@@ -543,6 +619,31 @@ def reference_batch(store: torch.Tensor, lut: torch.Tensor,
     return out.permute(0, 3, 1, 2).contiguous()
 
 
+def reference_batch_cutmix(store: torch.Tensor, lut: torch.Tensor,
+                           labels: torch.Tensor, index: torch.Tensor,
+                           pad: int, hflip: bool, seed: int, epoch: int,
+                           prob: float):
+    """CPU reference of the ``batch_gather_cutmix`` kernel: ``(images,
+    labels_a, labels_b, lam)`` with images = where(box, aug(j), aug(i)) —
+    two ``reference_batch`` calls and a mask; the partner j carries its own
+    (dx, dy, flip) of the epoch."""
+    N, H, W, C = store.shape
+    index = index.clamp(0, N - 1)
+    mp = cutmix_params(seed, epoch, index.numpy(), N, H, W, prob)
+    apply = torch.from_numpy(mp.apply).bool()
+    partner = torch.where(apply, torch.from_numpy(mp.j), index)
+    own = reference_batch(store, lut, index, pad, hflip, seed, epoch)
+    other = reference_batch(store, lut, partner, pad, hflip, seed, epoch)
+    x0, y0, x1, y1 = (torch.from_numpy(a).view(-1, 1, 1) for a in mp.box)
+    ys = torch.arange(H).view(1, H, 1)
+    xs = torch.arange(W).view(1, 1, W)
+    mask = (apply.view(-1, 1, 1) & (xs >= x0) & (xs < x1)
+            & (ys >= y0) & (ys < y1))                                # [B,H,W]
+    images = torch.where(mask.unsqueeze(1), other, own)
+    return (images, torch.index_select(labels, 0, index),
+            torch.index_select(labels, 0, partner), torch.from_numpy(mp.lam))
+
+
 class DeviceBatchLoader:
     """Batch loader over a device-resident uint8 copy of an in-memory
     dataset; same iteration contract as ``FastBatchLoader`` ((images,
@@ -558,6 +659,11 @@ class DeviceBatchLoader:
     Without a GPU (``device`` None or a CPU device) the same batches come
     from ``reference_batch`` as fp32 NCHW — the tests' oracle and the CPU
     training path.
+
+    With ``augment.cutmix_prob`` > 0 the batches are ``(images,
+    MixedTarget)`` from ``ext.batch_gather_cutmix`` (CPU:
+    ``reference_batch_cutmix``), still one launch per batch; with it off
+    nothing changes, the same call as before builds the batch.
 
     The device path sees every dataset at 8 bits: real MNIST/CIFAR files
     (k/255 values) round-trip exactly, the synthetic stand-ins are
@@ -589,6 +695,10 @@ class DeviceBatchLoader:
             nbytes = N * C * H * W
             free, _ = torch.cuda.mem_get_info(device)
             if nbytes > free // 2:
+                if self.augment.cutmix_prob > 0:
+                    raise RuntimeError(
+                        "CutMix needs the device-resident store, which does "
+                        "not fit in half of the free device memory")
                 print(f"[data] uint8 store of {nbytes / 2**20:.0f} MiB "
                       f"exceeds half of the free device memory "
                       f"({free / 2**20:.0f} MiB free); using the host "
@@ -622,6 +732,9 @@ class DeviceBatchLoader:
         epoch = int(getattr(self.sampler, "epoch", 0) or 0)
         aug = self.augment
         B = self.batch_size
+        if aug.cutmix_prob > 0:
+            yield from self._iter_cutmix(idx, epoch)
+            return
         if not self.gpu:
             for s0 in range(0, idx.numel(), B):
                 sel = idx[s0:s0 + B]
@@ -638,3 +751,25 @@ class DeviceBatchLoader:
                 self.store, self.labels, idx_dev[s0:s0 + B], self.lut,
                 aug.crop_pad, aug.hflip, seed, epoch)
             yield images, labels
+
+    def _iter_cutmix(self, idx, epoch):
+        from ..ops.functional import MixedTarget
+        aug = self.augment
+        B = self.batch_size
+        if not self.gpu:
+            for s0 in range(0, idx.numel(), B):
+                images, la, lb, lam = reference_batch_cutmix(
+                    self.store, self.lut, self.labels, idx[s0:s0 + B],
+                    aug.crop_pad, aug.hflip, self.seed, epoch,
+                    aug.cutmix_prob)
+                yield images, MixedTarget(la, lb, lam)
+            return
+        idx_dev = idx.to(self.device)     # one upload per epoch
+        seed = self.seed & _U64           # the binding takes it as int64 bits
+        seed = seed - (1 << 64) if seed >> 63 else seed
+        thresh = cutmix_threshold(aug.cutmix_prob)
+        for s0 in range(0, idx.numel(), B):
+            images, la, lb, lam = self._ext.batch_gather_cutmix(
+                self.store, self.labels, idx_dev[s0:s0 + B], self.lut,
+                aug.crop_pad, aug.hflip, seed, epoch, thresh)
+            yield images, MixedTarget(la, lb, lam)

@@ -63,7 +63,14 @@ def iterate_loader(
             apex_optimizer.zero_grad()
         with ph("h2d"):
             image = image.to(device, non_blocking=True)
-            target = target.to(device, dtype=torch.long, non_blocking=True)
+            if isinstance(target, F_ops.MixedTarget):
+                # CutMix loader: the loss takes the pair, accuracy counts
+                # against the class holding at least half of the weight
+                target = target.to(device, non_blocking=True)
+                hard_target = target.dominant()
+            else:
+                target = target.to(device, dtype=torch.long, non_blocking=True)
+                hard_target = target
         with ph("fwd"):
             outputs = model(image)
             batch_loss = loss_function(outputs, target)
@@ -77,7 +84,7 @@ def iterate_loader(
 
         # device-side metric accumulation (one host sync per epoch)
         loss_sum += batch_loss.detach().double() * image.shape[0]
-        correct_sum += F_ops.argmax_correct(outputs.detach(), target)
+        correct_sum += F_ops.argmax_correct(outputs.detach(), hard_target)
         num += image.shape[0]
 
     if training:

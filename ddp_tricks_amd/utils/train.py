@@ -81,18 +81,25 @@ def train(args):
     if augment_mode not in AUGMENT_MODES:
         raise ValueError(f"unknown augment mode {augment_mode!r}")
     normalize = bool(getattr(args, "normalize", False))
+    # --cutmix_prob (train loader only) lives in the same batch kernel, so
+    # it implies the device loader the way --augment does
+    cutmix_prob = float(getattr(args, "cutmix_prob", 0.0) or 0.0)
+    if not 0.0 <= cutmix_prob <= 1.0:
+        raise ValueError("--cutmix_prob must be in [0, 1]")
     device_data = (bool(getattr(args, "device_data", False))
-                   or augment_mode != "none" or normalize)
+                   or augment_mode != "none" or normalize or cutmix_prob > 0)
     if device_data and not hasattr(train_set, "images"):
-        raise ValueError("--device_data/--augment/--normalize need an "
-                         "in-memory dataset (one with an .images tensor)")
+        raise ValueError("--device_data/--augment/--normalize/--cutmix_prob "
+                         "need an in-memory dataset (one with an .images "
+                         "tensor)")
     if device_data:
         norm = dict(mean=Dataset.MEAN, std=Dataset.STD) if normalize else {}
         crop_pad, hflip = AUGMENT_MODES[augment_mode]
+        mix = dict(cutmix_prob=cutmix_prob) if cutmix_prob > 0 else {}
         train_loader = DeviceBatchLoader(
             train_set, args.batch_size, sampler=train_sampler,
             device=dev_arg, seed=args.seed_num,
-            augment=Augment(crop_pad=crop_pad, hflip=hflip, **norm))
+            augment=Augment(crop_pad=crop_pad, hflip=hflip, **norm, **mix))
     elif hasattr(train_set, "images"):   # in-memory tensors: vectorized path
         train_loader = FastBatchLoader(train_set, args.batch_size,
                                        sampler=train_sampler, pin_memory=pin,
@@ -152,6 +159,17 @@ def train(args):
                          momentum=0.9, nesterov=True)
     lookahead = Lookahead(optimizer=optimizer, k=10, alpha=0.5)
     from ..ops.functional import cross_entropy_loss as loss_function
+    # --label_smoothing binds into the TRAINING loss only; validation keeps
+    # the plain hard-target loss so valid_loss (plateau scheduler, early
+    # stopping) stays comparable with runs that do not smooth
+    label_smoothing = float(getattr(args, "label_smoothing", 0.0) or 0.0)
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError("--label_smoothing must be in [0, 1)")
+    train_loss_function = loss_function
+    if label_smoothing > 0:
+        import functools
+        train_loss_function = functools.partial(
+            loss_function, label_smoothing=label_smoothing)
     best_valid_acc = 0
 
     # LR warmup lambda (reference utils/train.py:48-51, incl. the dead
@@ -210,7 +228,7 @@ def train(args):
         parallel_model.train()
         train_loss, train_acc, curr_lr = iterate_loader(
             loader=train_loader, model=parallel_model,
-            loss_function=loss_function, local_rank=local_rank,
+            loss_function=train_loss_function, local_rank=local_rank,
             apex_optimizer=apex_optimizer, training=True)
 
         parallel_model.eval()

@@ -65,6 +65,13 @@ def parse_args():
                         help="convert every BatchNorm to SyncBatchNorm: "
                              "batch statistics over all ranks, one small "
                              "gather per layer and direction")
+    parser.add_argument("--label_smoothing", default=0.0, type=float,
+                        help="label smoothing of the training loss, in "
+                             "[0, 1); validation loss stays unsmoothed")
+    parser.add_argument("--cutmix_prob", default=0.0, type=float,
+                        help="per-sample CutMix probability on the train "
+                             "loader (alpha = 1 boxes); implies "
+                             "--device_data on GPU")
     args = parser.parse_args()
     if args.local_rank is None:
         args.local_rank = int(os.environ.get("LOCAL_RANK", 0))
