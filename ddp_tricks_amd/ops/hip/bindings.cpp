@@ -105,13 +105,17 @@ at::Tensor linear_wgrad(at::Tensor dy, at::Tensor x);
 
 // conv.hip
 at::Tensor conv2d_fwd(at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias,
-                      long stride, long pad);
+                      long stride, long pad, long kwalk);
 std::vector<at::Tensor> conv2d_fwd_stats(at::Tensor x, at::Tensor w,
                                          c10::optional<at::Tensor> bias,
-                                         long stride, long pad);
+                                         long stride, long pad, long kwalk);
 at::Tensor conv2d_dgrad(at::Tensor dy, at::Tensor wt2, long N, long C, long H,
                         long W, long R, long S, long stride, long pad,
-                        c10::optional<at::Tensor> addend, long group);
+                        c10::optional<at::Tensor> addend, long group,
+                        long kwalk);
+std::string conv2d_kloop_plan(long mode, long N, long C, long H, long W,
+                              long Ko, long R, long S, long stride, long pad,
+                              long kwalk);
 std::tuple<std::string, long, long, long> conv2d_dgrad_plan(
     long N, long C, long H, long W, long Ko, long R, long S, long stride,
     long pad, long group);
@@ -251,15 +255,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("linear_wgrad", &linear_wgrad);
     m.def("conv2d_fwd", &conv2d_fwd, py::arg("x"), py::arg("w"),
           py::arg("bias") = c10::nullopt, py::arg("stride") = 1,
-          py::arg("pad") = 0);
+          py::arg("pad") = 0, py::arg("kwalk") = -1);
     m.def("conv2d_fwd_stats", &conv2d_fwd_stats, py::arg("x"), py::arg("w"),
           py::arg("bias") = c10::nullopt, py::arg("stride") = 1,
-          py::arg("pad") = 0);
+          py::arg("pad") = 0, py::arg("kwalk") = -1);
     m.def("conv2d_dgrad", &conv2d_dgrad,
           py::arg("dy"), py::arg("wt2"), py::arg("N"), py::arg("C"),
           py::arg("H"), py::arg("W"), py::arg("R"), py::arg("S"),
           py::arg("stride"), py::arg("pad"),
-          py::arg("addend") = c10::nullopt, py::arg("group") = -1);
+          py::arg("addend") = c10::nullopt, py::arg("group") = -1,
+          py::arg("kwalk") = -1);
+    m.def("conv2d_kloop_plan", &conv2d_kloop_plan,
+          "'walk' or 'decode': the K loop conv2d_fwd[_stats] (mode 0) or "
+          "conv2d_dgrad (mode 1) would run for this shape; kwalk -1 "
+          "automatic, 0 decode, 1 forces the scalar tap walk; launches "
+          "nothing",
+          py::arg("mode"), py::arg("N"), py::arg("C"), py::arg("H"),
+          py::arg("W"), py::arg("Ko"), py::arg("R"), py::arg("S"),
+          py::arg("stride"), py::arg("pad"), py::arg("kwalk") = -1);
     m.def("conv2d_dgrad_plan", &conv2d_dgrad_plan,
           "(name, G, k_tiles_issued, k_tiles_raster) conv2d_dgrad would run "
           "for this shape; group -1 automatic, 0 raster, 32/64/128 forces "

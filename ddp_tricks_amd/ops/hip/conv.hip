@@ -16,6 +16,7 @@
 #include <climits>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include "common.h"
 
 typedef short bf16x8_t __attribute__((ext_vector_type(8)));
@@ -123,8 +124,17 @@ struct BnFuse {
 // operand streamed into the output epilogue (dx += addin): the ResNet
 // skip-gradient accumulation fused into the junction conv's dgrad
 // (VERDICT r01 next-round #4).
+//
+// WALK (MODE 0, and stride-1 MODE 1): the contraction channels (C forward,
+// Ko dgrad) are a multiple of CBK, so every K-tile lies inside one tap and
+// (r, s, channel base) are block-uniform.  The K loop then carries them as
+// scalars; a lane's source is a per-lane 64-bit byte offset cached once
+// (tap (0,0), its own channel segment) plus the tile's scalar tap offset,
+// and the bounds test is two adds and two unsigned compares.  No division,
+// no 64-bit multiply and no branch per chunk; LDS images, K-tile order and
+// MFMA order are those of the decode loop, so outputs are bit-identical.
 template <int MODE, int TBN, int WAVES_M, int WAVES_N, bool STRIDE1,
-          int CBM_T, bool TAPS = false>
+          int CBM_T, bool TAPS = false, bool WALK = false>
 __device__ __forceinline__
 void conv_gemm_body(const bf16* __restrict__ Asrc,
                     const bf16* __restrict__ Bsrc,
@@ -146,6 +156,8 @@ void conv_gemm_body(const bf16* __restrict__ Asrc,
     __shared__ bf16 lds_a[1][CBM_T][CBK];  // unpadded: glds dest is linear
     __shared__ bf16 lds_b[1][TBN][CBK];
     static_assert(!TAPS || (MODE == 1 && STRIDE1), "TAPS is stride-1 dgrad");
+    static_assert(!WALK || MODE == 0 || (MODE == 1 && STRIDE1),
+                  "WALK is forward or stride-1 dgrad");
     // TAPS: consecutive blockIdx.x land on different XCDs (b and b + 8 share
     // one), so where the tile count divides, hand XCD j the j-th eighth of
     // the tiles — the blocks resident on one XCD then walk neighbouring
@@ -174,12 +186,21 @@ void conv_gemm_body(const bf16* __restrict__ Asrc,
     constexpr int A_PER = A_CHUNKS / 4;
     long ri_nb[A_PER];
     int ri_u[A_PER], ri_v[A_PER];
+    // WALK: byte offset of the chunk's source at tap (0,0), channel segment
+    // seg = pl_segp ^ pl_row (the same in every chunk: chunk rows are
+    // multiples of 8 apart), and the row-valid predicate.  The wave index is
+    // made provably uniform so chunk indices and LDS targets are scalars.
+    long a_off[A_PER];
+    bool a_rv[A_PER];
+    const int walk_seg8 = (pl_segp ^ pl_row) * 8;
+    const int widu = WALK ? __builtin_amdgcn_readfirstlane(wid) : wid;
     #pragma unroll
     for (int ci = 0; ci < A_PER; ++ci) {
         const int ch = wid + ci * 4;
         const int row = ch * 8 + pl_row;
         const int gm = m0 + row;
         ri_u[ci] = INT_MIN;
+        if (WALK) { ri_v[ci] = 0; a_off[ci] = 0; a_rv[ci] = false; }
         if (gm < M) {
             if (MODE == 0) {
                 unsigned rem = fd_div(gm, cs.fdQ);
@@ -217,8 +238,75 @@ void conv_gemm_body(const bf16* __restrict__ Asrc,
                 ri_u[ci] = h + cs.pad;
                 ri_v[ci] = wcol + cs.pad;
             }
+            if (WALK) {
+                a_rv[ci] = true;
+                a_off[ci] = (((ri_nb[ci] + ri_u[ci]) * (MODE == 0 ? cs.W : cs.Q)
+                              + ri_v[ci]) * (MODE == 0 ? cs.C : cs.Ko)
+                             + walk_seg8) * (long)sizeof(bf16);
+            }
         }
     }
+    // WALK B side: a lane's row of chunk 0 and its segment are fixed; chunk
+    // bi is 32 rows (a block-uniform stride) further.
+    constexpr int B_PER = B_CHUNKS / 4;
+    long b_off = 0;
+    bool b_cv[B_PER];
+    if (WALK) {
+        b_off = ((long)(n0 + widu * 8 + pl_row) * Kgemm + walk_seg8)
+                * (long)sizeof(bf16);
+        #pragma unroll
+        for (int bi = 0; bi < B_PER; ++bi)
+            b_cv[bi] = n0 + (widu + bi * 4) * 8 + pl_row < Nout;
+    }
+    // the zero buffer's address, held in SGPRs (opaque to the compiler, or
+    // it re-materialises the address at every use)
+    unsigned long zaddr = reinterpret_cast<unsigned long>(g_zero16);
+    if (WALK) asm volatile("" : "+s"(zaddr));
+
+    // One K-tile of the WALK loop: tap (r, sx), channel base c0, all scalar.
+    auto issue_tile_walk = [&](int kt, int r, int sx, int c0, auto nopad_c) {
+        constexpr bool NOPAD = decltype(nopad_c)::value;
+        const int tap_off = MODE == 0 ? (r * cs.W + sx) * cs.C + c0
+                                      : c0 - (r * cs.Q + sx) * cs.Ko;
+        const unsigned long abase = reinterpret_cast<unsigned long>(Asrc)
+            + (unsigned long)((long)tap_off * (long)sizeof(bf16));
+        #pragma unroll
+        for (int ci = 0; ci < A_PER; ++ci) {
+            bool ok;
+            if (NOPAD)          // MODE 0, pad == 0: every tap of a row is inside
+                ok = a_rv[ci];
+            else if (MODE == 0)
+                ok = (unsigned)ri_u[ci] + (unsigned)r < (unsigned)cs.H &&
+                     (unsigned)ri_v[ci] + (unsigned)sx < (unsigned)cs.W;
+            else
+                ok = (unsigned)ri_u[ci] - (unsigned)r < (unsigned)cs.P &&
+                     (unsigned)ri_v[ci] - (unsigned)sx < (unsigned)cs.Q;
+            const unsigned long addr =
+                ok ? abase + (unsigned long)a_off[ci] : zaddr;
+            __builtin_amdgcn_global_load_lds(
+                reinterpret_cast<const __attribute__((address_space(1)))
+                                 unsigned short*>(addr),
+                (__attribute__((address_space(3))) unsigned short*)
+                    &lds_a[0][(widu + ci * 4) * 8][0],
+                16, 0, 0);
+        }
+        const unsigned long bbase = reinterpret_cast<unsigned long>(Bsrc)
+            + (unsigned long)((long)kt * (long)sizeof(bf16));
+        #pragma unroll
+        for (int bi = 0; bi < B_PER; ++bi) {
+            const unsigned long addr = b_cv[bi]
+                ? bbase + (unsigned long)((long)bi * 32 * Kgemm
+                                          * (long)sizeof(bf16))
+                      + (unsigned long)b_off
+                : zaddr;
+            __builtin_amdgcn_global_load_lds(
+                reinterpret_cast<const __attribute__((address_space(1)))
+                                 unsigned short*>(addr),
+                (__attribute__((address_space(3))) unsigned short*)
+                    &lds_b[0][(widu + bi * 4) * 8][0],
+                16, 0, 0);
+        }
+    };
 
     auto issue_tile = [&](int kt, int buf) {
         // ---- A tile: chunks round-robined over the 4 waves ----
@@ -311,13 +399,8 @@ void conv_gemm_body(const bf16* __restrict__ Asrc,
         tap_mask = __builtin_amdgcn_readfirstlane(dgrad_tap_mask(
             m0, min(m0 + CBM_T, M) - 1, (int)cs.fdGHW.d, cs.lgG, cs.H, cs.W,
             cs.P, cs.Q, cs.R, cs.S, cs.pad));
-    int tap = 0, tap_end = cs.Ko;       // [tap_end - Ko, tap_end) is tap's k
-    for (int kt = 0; kt < Kgemm; kt += CBK) {
-        if (TAPS) {
-            if (kt == tap_end) { ++tap; tap_end += cs.Ko; }
-            if (!((tap_mask >> tap) & 1u)) { kt = tap_end - CBK; continue; }
-        }
-        issue_tile(kt, 0);
+    // the MFMA phase of one K-tile, shared by both loops
+    auto mma_tile = [&]() {
         __syncthreads();   // vmcnt(0) for the in-flight glds + barrier
         #pragma unroll
         for (int ks = 0; ks < CBK; ks += 32) {
@@ -343,6 +426,37 @@ void conv_gemm_body(const bf16* __restrict__ Asrc,
                         af[mi], bfr[ni], acc[mi][ni], 0, 0, 0);
         }
         __syncthreads();
+    };
+    // WALK: one tap state (r, sx, c0, tap = r*S + sx), all scalar, serves
+    // the tile's addresses and the TAPS skip.  K-tiles run in the decode
+    // loop's order: c0 fastest, then sx, then r.
+    auto walk_loop = [&](auto nopad_c) {
+        const int Cd = MODE == 0 ? cs.C : cs.Ko;
+        int kt = 0, tap = 0;
+        for (int r = 0; r < cs.R; ++r)
+            for (int sx = 0; sx < cs.S; ++sx, ++tap, kt += Cd) {
+                if (TAPS && !((tap_mask >> tap) & 1u)) continue;
+                for (int c0 = 0; c0 < Cd; c0 += CBK) {
+                    issue_tile_walk(kt + c0, r, sx, c0, nopad_c);
+                    mma_tile();
+                }
+            }
+    };
+    if (WALK) {
+        // pad == 0 forward: block-uniform choice of the loop without the
+        // bounds test
+        if (MODE == 0 && cs.pad == 0) walk_loop(std::true_type{});
+        else walk_loop(std::false_type{});
+    } else {
+        int tap = 0, tap_end = cs.Ko;   // [tap_end - Ko, tap_end) is tap's k
+        for (int kt = 0; kt < Kgemm; kt += CBK) {
+            if (TAPS) {
+                if (kt == tap_end) { ++tap; tap_end += cs.Ko; }
+                if (!((tap_mask >> tap) & 1u)) { kt = tap_end - CBK; continue; }
+            }
+            issue_tile(kt, 0);
+            mma_tile();
+        }
     }
 
     float psum[NI] = {}, psq[NI] = {};
@@ -536,7 +650,7 @@ void conv_gemm_body(const bf16* __restrict__ Asrc,
 }
 
 template <int MODE, int TBN, int WAVES_M, int WAVES_N, bool STRIDE1 = true,
-          int CBM_T = CBM, bool TAPS = false>
+          int CBM_T = CBM, bool TAPS = false, bool WALK = false>
 // min-4-waves/SIMD bound: the allocator packs the body into 122 arch
 // VGPRs (no AGPRs, zero spills) instead of 84V+64A, lifting residency
 // 3 -> 4 blocks/CU on the 128-wide tiles (and 4 -> 5 on the 64-wide) —
@@ -548,7 +662,7 @@ void k_conv_gemm(const bf16* __restrict__ Asrc, const bf16* __restrict__ Bsrc,
                  float* __restrict__ stats = nullptr,
                  BnFuse bn = BnFuse{},
                  const bf16* __restrict__ addin = nullptr) {
-    conv_gemm_body<MODE, TBN, WAVES_M, WAVES_N, STRIDE1, CBM_T, TAPS>(
+    conv_gemm_body<MODE, TBN, WAVES_M, WAVES_N, STRIDE1, CBM_T, TAPS, WALK>(
         Asrc, Bsrc, bias, out, cs, M, Kgemm, Nout, stats, bn, addin);
 }
 
@@ -1543,6 +1657,34 @@ static at::Tensor empty_nhwc(const at::Tensor& like, long n, long c, long h,
                      like.options().memory_format(at::MemoryFormat::ChannelsLast));
 }
 
+// K loop of k_conv_gemm: "walk" (scalar tap walk, the WALK instantiations)
+// or "decode" (per-chunk address decode).  The one place that decides; pure
+// host arithmetic.  kwalk: -1 automatic, 0 decode, 1 forces walk; a forced
+// walk on a shape it does not fit runs decode, and the plan says so.  Walk
+// fits MODE 0 with C % CBK == 0 and stride-1 MODE 1 with Ko % CBK == 0 (a
+// K-tile inside one tap); the kernel's tap offset is an int, its per-lane
+// offsets are 64-bit.
+static const char* plan_kloop(int mode, const ConvShape& cs, long kwalk) {
+    TORCH_CHECK(kwalk >= -1 && kwalk <= 1, "conv kwalk must be -1 "
+                "(automatic), 0 (decode) or 1 (walk); got ", kwalk);
+    bool fits = false;
+    // the tap offset the kernel forms, (r*W + s)*C + c0 with r < R, s < S
+    // (Q and Ko for dgrad), must fit its int
+    if (mode == 0)
+        fits = cs.C % CBK == 0 &&
+               ((long)cs.R * cs.W + cs.S) * cs.C < INT_MAX;
+    else if (mode == 1)
+        fits = cs.stride == 1 && cs.Ko % CBK == 0 &&
+               ((long)cs.R * cs.Q + cs.S) * cs.Ko < INT_MAX;
+    if (!fits || kwalk == 0) return "decode";
+    // Automatic is the fit rule: the walk loop runs a subset of the decode
+    // loop's instructions on the same data in the same order, so there is no
+    // shape-dependent trade, and no class measured was slower (every one is
+    // 20-30 % faster by its median: tools/bench_kernels.py --kwalk,
+    // docs/KERNELS.md).
+    return "walk";
+}
+
 // The one tile choice of forward and dgrad: a 128-channel output tile on
 // 2x2 waves from 128 output channels up, else (or with narrow) 64 channels
 // on 4x1 waves.
@@ -1555,7 +1697,26 @@ static void launch_conv_gemm(hipStream_t stream, int grid_m, int n_channels,
                              bool narrow, const bf16* Asrc, const bf16* Bsrc,
                              const float* bias, bf16* out,
                              const ConvShape& cs, long M, int Kgemm,
-                             float* stats, BnFuse bn, const bf16* addin) {
+                             float* stats, BnFuse bn, const bf16* addin,
+                             long kwalk = 0) {
+    if constexpr (MODE != 2) {
+        if (plan_kloop(MODE, cs, kwalk)[0] == 'w') {
+            if (n_channels >= 128 && !narrow)
+                hipLaunchKernelGGL(
+                    (k_conv_gemm<MODE, 128, 2, 2, STRIDE1, CBM, false, true>),
+                    dim3(grid_m, ceil_div_i(n_channels, 128)), dim3(256), 0,
+                    stream, Asrc, Bsrc, bias, out, cs, (int)M, Kgemm,
+                    n_channels, stats, bn, addin);
+            else
+                hipLaunchKernelGGL(
+                    (k_conv_gemm<MODE, 64, 4, 1, STRIDE1, CBM, false, true>),
+                    dim3(grid_m, ceil_div_i(n_channels, 64)), dim3(256), 0,
+                    stream, Asrc, Bsrc, bias, out, cs, (int)M, Kgemm,
+                    n_channels, stats, bn, addin);
+            HIP_CHECK_LAST();
+            return;
+        }
+    }
     if (n_channels >= 128 && !narrow)
         hipLaunchKernelGGL((k_conv_gemm<MODE, 128, 2, 2, STRIDE1>),
                            dim3(grid_m, ceil_div_i(n_channels, 128)),
@@ -1592,7 +1753,7 @@ static void launch_conv_gemm_cls(hipStream_t stream, int grid_m,
 static std::vector<at::Tensor> conv_fwd_impl(
         const at::Tensor& x, const at::Tensor& w,
         const c10::optional<at::Tensor>& bias, long stride, long pad,
-        bool want_stats) {
+        bool want_stats, long kwalk) {
     // x: NCHW logical / channels_last physical bf16; w: KCRS logical /
     // channels_last physical (= KRSC memory) bf16
     TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16);
@@ -1608,6 +1769,7 @@ static std::vector<at::Tensor> conv_fwd_impl(
     bf16* yp = reinterpret_cast<bf16*>(y.data_ptr());
 
     if (cs.C < 8 && !want_stats) {
+        plan_kloop(0, cs, kwalk);           // validates kwalk
         TORCH_CHECK(cs.Ko % 8 == 0);
         int lds = cs.Ko * Kgemm * 2;
         long total = M * (cs.Ko / 8);
@@ -1631,19 +1793,20 @@ static std::vector<at::Tensor> conv_fwd_impl(
     launch_conv_gemm<0>(stream.stream(), gridM, cs.Ko,
                         tbn_env && !want_stats, xp, wp, bp, yp, cs, M, Kgemm,
                         want_stats ? slab.data_ptr<float>() : nullptr,
-                        BnFuse{}, nullptr);
+                        BnFuse{}, nullptr, kwalk);
     return {y, slab};
 }
 
 at::Tensor conv2d_fwd(at::Tensor x, at::Tensor w,
-                      c10::optional<at::Tensor> bias, long stride, long pad) {
-    return conv_fwd_impl(x, w, bias, stride, pad, false)[0];
+                      c10::optional<at::Tensor> bias, long stride, long pad,
+                      long kwalk) {
+    return conv_fwd_impl(x, w, bias, stride, pad, false, kwalk)[0];
 }
 
 std::vector<at::Tensor> conv2d_fwd_stats(at::Tensor x, at::Tensor w,
                                          c10::optional<at::Tensor> bias,
-                                         long stride, long pad) {
-    return conv_fwd_impl(x, w, bias, stride, pad, true);
+                                         long stride, long pad, long kwalk) {
+    return conv_fwd_impl(x, w, bias, stride, pad, true, kwalk);
 }
 
 // dy: NCHW logical / channels_last bf16 [N,Ko,P,Q]; wt2: [C, R*S*Ko] bf16
@@ -1737,7 +1900,7 @@ static DgradPlan plan_dgrad(const ConvShape& cs, bool want_bn, long group) {
 static at::Tensor dgrad_stride1(const at::Tensor& dy, const at::Tensor& wt2,
                                 ConvShape cs,
                                 const c10::optional<at::Tensor>& addend,
-                                BnFuse bn, long group) {
+                                BnFuse bn, long group, long kwalk) {
     auto dx = empty_nhwc(dy, cs.N, cs.C, cs.H, cs.W);
     const bf16* adp = nullptr;
     if (addend.has_value()) {
@@ -1755,36 +1918,42 @@ static at::Tensor dgrad_stride1(const at::Tensor& dy, const at::Tensor& wt2,
     const DgradPlan plan = plan_dgrad(cs, bn.slab != nullptr, group);
     if (plan.G == 0) {
         launch_conv_gemm<1>(stream, grid_m, cs.C, false, dyp, wtp, nullptr,
-                            dxp, cs, M, Kgemm, nullptr, bn, adp);
+                            dxp, cs, M, Kgemm, nullptr, bn, adp, kwalk);
         return dx;
     }
     // tap-uniform row order: same tiles, grid and arguments, rows permuted
     cs.fdGHW.init((unsigned)plan.G * cs.H * cs.W);
     cs.lgG = 0;
     while ((1 << cs.lgG) < plan.G) ++cs.lgG;
-    if (cs.C >= 128)
-        hipLaunchKernelGGL((k_conv_gemm<1, 128, 2, 2, true, CBM, true>),
-                           dim3(grid_m, ceil_div_i(cs.C, 128)), dim3(256), 0,
-                           stream, dyp, wtp, nullptr, dxp, cs, (int)M, Kgemm,
-                           cs.C, nullptr, BnFuse{}, adp);
-    else
-        hipLaunchKernelGGL((k_conv_gemm<1, 64, 4, 1, true, CBM, true>),
-                           dim3(grid_m, ceil_div_i(cs.C, 64)), dim3(256), 0,
-                           stream, dyp, wtp, nullptr, dxp, cs, (int)M, Kgemm,
-                           cs.C, nullptr, BnFuse{}, adp);
+    const bool walk = plan_kloop(1, cs, kwalk)[0] == 'w';
+    const dim3 grid(grid_m, ceil_div_i(cs.C, cs.C >= 128 ? 128 : 64));
+    auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, dyp, wtp,
+                           (const float*)nullptr, dxp, cs, (int)M, Kgemm,
+                           cs.C, (float*)nullptr, BnFuse{}, adp);
+    };
+    if (cs.C >= 128) {
+        if (walk) launch(k_conv_gemm<1, 128, 2, 2, true, CBM, true, true>);
+        else launch(k_conv_gemm<1, 128, 2, 2, true, CBM, true, false>);
+    } else {
+        if (walk) launch(k_conv_gemm<1, 64, 4, 1, true, CBM, true, true>);
+        else launch(k_conv_gemm<1, 64, 4, 1, true, CBM, true, false>);
+    }
     HIP_CHECK_LAST();
     return dx;
 }
 
 at::Tensor conv2d_dgrad(at::Tensor dy, at::Tensor wt2, long N, long C,
                         long H, long W, long R, long S, long stride, long pad,
-                        c10::optional<at::Tensor> addend, long group) {
+                        c10::optional<at::Tensor> addend, long group,
+                        long kwalk) {
     ConvShape cs = dgrad_shape(dy, N, C, H, W, R, S, stride, pad);
     TORCH_CHECK(!addend.has_value() || cs.stride == 1,
                 "fused dgrad addend needs stride 1");
     if (cs.stride == 1)
-        return dgrad_stride1(dy, wt2, cs, addend, BnFuse{}, group);
+        return dgrad_stride1(dy, wt2, cs, addend, BnFuse{}, group, kwalk);
     plan_dgrad(cs, false, group);       // validates group; strided is raster
+    plan_kloop(1, cs, kwalk);           // validates kwalk; strided is decode
 
     // NOTE: zero-stuffing dy to reach the stride-1 gather was tried and
     // REVERTED — measured slower at ResNet's strided shapes (r18 3x3/2:
@@ -1893,7 +2062,7 @@ std::vector<at::Tensor> conv2d_dgrad_bn(at::Tensor dy, at::Tensor wt2,
     bn.mean = bn_mean.data_ptr<float>();
     bn.invstd = bn_invstd.data_ptr<float>();
     bn.slab = slab.data_ptr<float>();
-    return {dgrad_stride1(dy, wt2, cs, c10::nullopt, bn, -1), slab};
+    return {dgrad_stride1(dy, wt2, cs, c10::nullopt, bn, -1, -1), slab};
 }
 
 // (name, G, k_tiles_issued, k_tiles_raster) conv2d_dgrad would run for this
@@ -1911,6 +2080,20 @@ std::tuple<std::string, long, long, long> conv2d_dgrad_plan(
     const DgradPlan p = plan_dgrad(cs, false, group);
     return std::make_tuple(std::string(p.name), (long)p.G, p.k_tiles,
                            p.k_tiles_raster);
+}
+
+// "walk" or "decode": the K loop conv2d_fwd[_stats] (mode 0) or conv2d_dgrad
+// (mode 1) would run for this shape and kwalk argument; no tensors, launches
+// nothing.
+std::string conv2d_kloop_plan(long mode, long N, long C, long H, long W,
+                              long Ko, long R, long S, long stride, long pad,
+                              long kwalk) {
+    TORCH_CHECK(mode == 0 || mode == 1, "mode is 0 (forward) or 1 (dgrad)");
+    TORCH_CHECK(N > 0 && C > 0 && Ko > 0 && R > 0 && S > 0 && stride > 0 &&
+                pad >= 0 && H + 2 * pad >= R && W + 2 * pad >= S);
+    ConvShape cs = make_shape((int)N, (int)C, (int)H, (int)W, (int)Ko, (int)R,
+                              (int)S, (int)stride, (int)pad);
+    return plan_kloop((int)mode, cs, kwalk);
 }
 
 at::Tensor col_sum(at::Tensor x);   // gemm.hip

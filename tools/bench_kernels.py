@@ -6,6 +6,7 @@ Usage (on a GPU box):  python tools/bench_kernels.py [--resnet]
                        python tools/bench_kernels.py --wgradbias
                        python tools/bench_kernels.py --wgraddma [--leaves wt3]
                        python tools/bench_kernels.py --dgradtaps
+                       python tools/bench_kernels.py --kwalk
 
 Times conv fwd/dgrad/wgrad per shape with HIP events (200 reps after 20
 warmup) and prints achieved TFLOP/s next to microseconds, so kernel A/B
@@ -445,6 +446,62 @@ def bench_dgradtaps(rounds, groups):
         torch.cuda.empty_cache()
 
 
+def bench_kwalk(rounds):
+    """K loop of k_conv_gemm: per-chunk address decode (kwalk 0) against the
+    scalar tap walk (kwalk 1), alternated in one process (`kwalk` is an
+    argument).  Forward goes through conv2d_fwd_stats as the training step
+    calls it; dgrad runs the row order the automatic plan picks at B = 1024
+    (conv2 raster, conv3 and conv4 tap-uniform at G = 128).  Controls: a 3x3
+    pad-1 stride-1 and a 3x3 pad-1 stride-2 ResNet layer.  Outputs are
+    checked equal before timing; 30 warm-up calls, then device events
+    around 10 calls, median/min/max over `rounds`."""
+    ext = load_extension(required=True)
+    dev = torch.device("cuda:0")
+    by_name = {s[0]: s for s in TOYNET + RESNET}
+    rows = [("fwd", n, 0) for n in ("conv2", "conv3", "conv4")]
+    rows += [("dgrad", "conv2", 0), ("dgrad", "conv3", 128),
+             ("dgrad", "conv4", 128)]
+    rows += [("fwd", "r18s1", 0), ("dgrad", "r18s1", 0), ("fwd", "r18s2", 0)]
+    print(f"{'op':6s} {'shape':8s} {'kwalk':>5s} {'plan':7s} {'med us':>9s} "
+          f"{'min':>9s} {'max':>9s} {'vs decode':>9s} {'TFLOP/s':>8s}")
+    for op, name, G in rows:
+        _, N, C, H, W, K, R, stride, pad = by_name[name]
+        P = (H + 2 * pad - R) // stride + 1
+        flops = 2.0 * N * P * P * K * C * R * R
+        g = torch.Generator(device=dev).manual_seed(0)
+        if op == "fwd":
+            x = torch.randn(N, C, H, W, device=dev, generator=g) \
+                .to(torch.bfloat16).contiguous(memory_format=CL)
+            w = torch.randn(K, C, R, R, device=dev, generator=g) \
+                .to(torch.bfloat16).contiguous(memory_format=CL)
+            call = (lambda kw: ext.conv2d_fwd_stats(x, w, None, stride, pad,
+                                                    kw))
+            plan = (lambda kw: ext.conv2d_kloop_plan(0, N, C, H, W, K, R, R,
+                                                     stride, pad, kw))
+        else:
+            dy = torch.randn(N, K, P, P, device=dev, generator=g) \
+                .to(torch.bfloat16).contiguous(memory_format=CL)
+            wt2 = torch.randn(C, R * R * K, device=dev, generator=g) \
+                .to(torch.bfloat16)
+            call = (lambda kw: [ext.conv2d_dgrad(dy, wt2, N, C, H, W, R, R,
+                                                 stride, pad, None, G, kw)])
+            plan = (lambda kw: ext.conv2d_kloop_plan(1, N, C, H, W, K, R, R,
+                                                     stride, pad, kw))
+        for a, b in zip(call(0), call(1)):
+            if not torch.equal(a, b):
+                raise RuntimeError(f"{op} {name}: walk differs from decode")
+        # 30 warm-up calls per variant: the first timed round must not be
+        # the one in which the allocator and the clocks settle
+        res = _time_alternating({kw: (lambda kw=kw: call(kw))
+                                 for kw in (0, 1)}, rounds=rounds, warmup=30)
+        for kw in (0, 1):
+            med, lo, hi = res[kw]
+            print(f"{op:6s} {name:8s} {kw:5d} {plan(kw):7s} {med:9.1f} "
+                  f"{lo:9.1f} {hi:9.1f} {med / res[0][0]:9.3f} "
+                  f"{flops / med / 1e6:8.1f}", flush=True)
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clip", action="store_true")
@@ -459,6 +516,7 @@ def main():
     ap.add_argument("--groups", default="0,32,64,128",
                     help="conv2d_dgrad group values for --dgradtaps, raster "
                          "(0) first")
+    ap.add_argument("--kwalk", action="store_true")
     ap.add_argument("--resnet", action="store_true")
     ap.add_argument("--functional", action="store_true")
     ap.add_argument("--bn", action="store_true")
@@ -480,6 +538,9 @@ def main():
     if args.dgradtaps:
         bench_dgradtaps(rounds=30,
                         groups=[int(v) for v in args.groups.split(",")])
+        return
+    if args.kwalk:
+        bench_kwalk(rounds=30)
         return
     if args.bn:
         bench_bn(args.reps)
