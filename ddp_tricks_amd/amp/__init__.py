@@ -116,14 +116,15 @@ def _clip_buffers(device, nchunks: int = 0):
 
 
 def _clip_fused(optimizer) -> bool:
-    """Lazy clip only when the step that follows is the fused SGD (possibly
-    under Lookahead) — it is the one consumer of the pending coefficient;
-    any other optimizer gets its gradients clipped in place."""
+    """Lazy clip only when the step that follows is the fused SGD or the
+    fused LARS (possibly under Lookahead) — they are the consumers of the
+    pending coefficient; any other optimizer gets its gradients clipped in
+    place."""
     if os.environ.get("DDPX_CLIP_FUSED", "1") == "0":
         return False
-    from ..ops.optim import FusedSGD
+    from ..ops.optim import FusedLARS, FusedSGD
     inner = optimizer
-    while inner is not None and not isinstance(inner, FusedSGD):
+    while inner is not None and not isinstance(inner, (FusedSGD, FusedLARS)):
         inner = getattr(inner, "optimizer", None)
     return inner is not None
 

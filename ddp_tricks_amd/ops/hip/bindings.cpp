@@ -16,6 +16,12 @@ void fused_sgd(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
                std::vector<at::Tensor> bufs, double lr, double momentum,
                double wd, double nesterov, c10::optional<at::Tensor> found_inf,
                c10::optional<at::Tensor> grad_scale);
+void fused_lars(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
+                std::vector<at::Tensor> bufs, at::Tensor partials,
+                at::Tensor ratios, double lr, double momentum, double wd,
+                double nesterov, double eta, double eps, bool trust_clip,
+                c10::optional<at::Tensor> found_inf,
+                c10::optional<at::Tensor> grad_scale);
 void fused_lookahead(std::vector<at::Tensor> fast, std::vector<at::Tensor> slow,
                      double alpha, c10::optional<at::Tensor> found_inf);
 at::Tensor cast_to_bf16(at::Tensor x);
@@ -169,6 +175,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("fused_sgd", &fused_sgd, "fused nesterov-momentum SGD step",
           py::arg("params"), py::arg("grads"), py::arg("bufs"), py::arg("lr"),
           py::arg("momentum"), py::arg("wd"), py::arg("nesterov"),
+          py::arg("found_inf") = c10::nullopt,
+          py::arg("grad_scale") = c10::nullopt);
+    m.def("fused_lars", &fused_lars,
+          "fused LARS step: per-tensor trust ratios (two partials per chunk, "
+          "one ratio per tensor, list order) applied inside the SGD step",
+          py::arg("params"), py::arg("grads"), py::arg("bufs"),
+          py::arg("partials"), py::arg("ratios"), py::arg("lr"),
+          py::arg("momentum"), py::arg("wd"), py::arg("nesterov"),
+          py::arg("eta"), py::arg("eps"), py::arg("trust_clip"),
           py::arg("found_inf") = c10::nullopt,
           py::arg("grad_scale") = c10::nullopt);
     m.def("fused_lookahead", &fused_lookahead, "fused Lookahead interpolation",

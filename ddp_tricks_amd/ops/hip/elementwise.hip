@@ -7,6 +7,8 @@
 // clipping rides on the same two passes: per-chunk sums of squares out of
 // the unscale kernel, a one-block finalize (norm + clip coefficient, on
 // device), and the coefficient applied inside the SGD's gradient read.
+// Fused LARS adds per-tensor reductions on the same (tensor, chunk) scheme:
+// pair square sums, a per-tensor trust ratio, and the SGD body with it.
 //
 // Multi-tensor scheme: host packs up to MT_MAX tensor pointers + a prefix
 // of chunk offsets into the kernarg struct; blocks map to (tensor, chunk)
@@ -427,6 +429,255 @@ void fused_sgd(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
                                (float)momentum, (float)wd, (float)nesterov,
                                fi, gs);
         HIP_CHECK_LAST();
+    }
+}
+
+// -------------------------------------------------------------- fused LARS ---
+
+// Layer-wise trust ratios (LARC "scale" formula) on the multi-tensor SGD
+// path, three launches per MT_MAX group, each a device-side no-op when
+// found_inf is set:
+//   1. k_mt_lars_sqsum  per (tensor, chunk): sum p^2 and sum (g*gs)^2
+//   2. k_mt_lars_ratio  per tensor: r = eta*|p| / (|g| + wd*|p| + eps)
+//   3. k_mt_lars        k_mt_sgd's body with gi *= r before the momentum
+// The ratio is a function of the partials alone (one block per tensor, a
+// fixed summation order), so every block of a tensor steps with the same
+// bits and the result does not depend on the grid.
+
+// Same element->thread mapping and fmaf order as mt_chunk_pass<false, true>:
+// with GS=false a chunk's g partial is bitwise k_mt_sqsum's.  GS squares
+// __fmul_rn(g, gs), the value k_mt_scale would have left in memory, so the
+// ratio is the same whether the clip was lazy or in place.
+// partials[2*c] = sum p^2, partials[2*c+1] = sum g^2, c the global chunk.
+template <bool GS>
+__global__ void k_mt_lars_sqsum(MTMeta m, const float* __restrict__ found_inf,
+                                const float* __restrict__ grad_scale,
+                                float* __restrict__ partials, int chunk_base) {
+    if (found_inf && *found_inf != 0.0f) return;
+    const float gs = GS ? *grad_scale : 1.0f;
+    int t; long base, end;
+    chunk_range(m, t, base, end);
+    const float* __restrict__ g = m.a[t];
+    const float* __restrict__ p = m.b[t];
+    float accp = 0.f, accg = 0.f;
+    long vb = base >> 2, ve = end >> 2;
+    for (long i = vb + threadIdx.x; i < ve; i += MT_BLOCK) {
+        f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+        f32x4 pv = reinterpret_cast<const f32x4*>(p)[i];
+        #pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float gj = gv[j];
+            if (GS) gj = __fmul_rn(gj, gs);
+            accg = fmaf(gj, gj, accg);
+            accp = fmaf(pv[j], pv[j], accp);
+        }
+    }
+    for (long i = ve * 4 + threadIdx.x; i < end; i += MT_BLOCK) {
+        float gj = g[i];
+        if (GS) gj = __fmul_rn(gj, gs);
+        accg = fmaf(gj, gj, accg);
+        accp = fmaf(p[i], p[i], accp);
+    }
+    float sp = mt_block_sum(accp);
+    __syncthreads();  // mt_block_sum's LDS is reused by the second sum
+    float sg = mt_block_sum(accg);
+    if (threadIdx.x == 0) {
+        long c = (long)chunk_base + blockIdx.x;
+        partials[2 * c] = sp;
+        partials[2 * c + 1] = sg;
+    }
+}
+
+// One block per tensor.  Thread i sums the tensor's chunk partials i,
+// i+MT_BLOCK, ... in double (a tensor may have thousands of chunks), then a
+// fixed LDS tree; thread 0 forms the ratio in double and rounds it once.
+// Zero-size tensors have no chunks: both norms are 0 and the ratio is 1.
+__global__ void k_mt_lars_ratio(MTMeta m, const float* __restrict__ partials,
+                                int chunk_base, float* __restrict__ ratios,
+                                int tensor_base, double lr, double wd,
+                                double eta, double eps, int trust_clip,
+                                const float* __restrict__ found_inf) {
+    if (found_inf && *found_inf != 0.0f) return;
+    __shared__ double redp[MT_BLOCK];
+    __shared__ double redg[MT_BLOCK];
+    const int t = blockIdx.x;
+    const int c0 = m.chunk_start[t], c1 = m.chunk_start[t + 1];
+    double sp = 0.0, sg = 0.0;
+    for (int c = c0 + threadIdx.x; c < c1; c += MT_BLOCK) {
+        long k = 2 * ((long)chunk_base + c);
+        sp += (double)partials[k];
+        sg += (double)partials[k + 1];
+    }
+    redp[threadIdx.x] = sp;
+    redg[threadIdx.x] = sg;
+    __syncthreads();
+    #pragma unroll
+    for (int w = MT_BLOCK / 2; w > 0; w >>= 1) {
+        if (threadIdx.x < w) {
+            redp[threadIdx.x] += redp[threadIdx.x + w];
+            redg[threadIdx.x] += redg[threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const double wn = sqrt(redp[0]), gn = sqrt(redg[0]);
+    double r = 1.0;
+    if (wn > 0.0 && gn > 0.0) {
+        r = eta * wn / (gn + wd * wn + eps);
+        if (trust_clip) r = fmin(r / lr, 1.0);
+    }
+    ratios[tensor_base + t] = (float)r;
+}
+
+// k_mt_sgd with the tensor's trust ratio applied to the decayed gradient:
+// gi = (g*gs + wd*p) * r, rounded once, i.e. bitwise k_mt_scale(g, r)
+// followed by k_mt_sgd when wd == 0.
+template <bool GS>
+__global__ void k_mt_lars(MTMeta m, float lr, float mu, float wd,
+                          float nesterov, const float* __restrict__ found_inf,
+                          const float* __restrict__ grad_scale,
+                          const float* __restrict__ ratios, int tensor_base) {
+    if (found_inf && *found_inf != 0.0f) return;
+    const float gs = GS ? *grad_scale : 1.0f;
+    int t; long base, end;
+    chunk_range(m, t, base, end);
+    const float r = ratios[tensor_base + t];
+    const float* __restrict__ g = m.a[t];
+    float* __restrict__ p = m.b[t];
+    float* __restrict__ buf = m.c[t];
+    long vb = base >> 2, ve = end >> 2;
+    for (long i = vb + threadIdx.x; i < ve; i += MT_BLOCK) {
+        f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+        f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
+        f32x4 bv = mu != 0.f ? reinterpret_cast<f32x4*>(buf)[i] : f32x4{};
+        #pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float gi = gv[j];
+            if (GS) gi = __fmul_rn(gi, gs);
+            if (wd != 0.0f) gi = fmaf(wd, pv[j], gi);
+            gi = __fmul_rn(gi, r);
+            float d = gi;
+            if (mu != 0.0f) {
+                float b = fmaf(mu, bv[j], gi);
+                bv[j] = b;
+                d = (nesterov != 0.0f) ? fmaf(mu, b, gi) : b;
+            }
+            pv[j] = fmaf(-lr, d, pv[j]);
+        }
+        reinterpret_cast<f32x4*>(p)[i] = pv;
+        if (mu != 0.f) reinterpret_cast<f32x4*>(buf)[i] = bv;
+    }
+    for (long i = ve * 4 + threadIdx.x; i < end; i += MT_BLOCK) {
+        float gi = g[i];
+        if (GS) gi = __fmul_rn(gi, gs);
+        if (wd != 0.0f) gi = fmaf(wd, p[i], gi);
+        gi = __fmul_rn(gi, r);
+        float d = gi;
+        if (mu != 0.0f) {
+            float b = fmaf(mu, buf[i], gi);
+            buf[i] = b;
+            d = (nesterov != 0.0f) ? fmaf(mu, b, gi) : b;
+        }
+        p[i] = fmaf(-lr, d, p[i]);
+    }
+}
+
+// partials: 2 floats per (tensor, chunk); ratios: one float per tensor, in
+// list order.  Both are indexed globally over the whole list, so the MT_MAX
+// launch groups write disjoint ranges.
+void fused_lars(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
+                std::vector<at::Tensor> bufs, at::Tensor partials,
+                at::Tensor ratios, double lr, double momentum, double wd,
+                double nesterov, double eta, double eps, bool trust_clip,
+                c10::optional<at::Tensor> found_inf,
+                c10::optional<at::Tensor> grad_scale) {
+    TORCH_CHECK(params.size() == grads.size());
+    bool has_mu = momentum != 0.0;
+    TORCH_CHECK(!has_mu || bufs.size() == params.size());
+    TORCH_CHECK(params.size() < (1UL << 30), "fused_lars: list too long");
+    for (size_t i = 0; i < params.size(); ++i) {
+        auto& p = params[i];
+        auto& g = grads[i];
+        TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat &&
+                    p.is_contiguous() && g.is_cuda() &&
+                    g.scalar_type() == at::kFloat && g.is_contiguous() &&
+                    g.numel() == p.numel(),
+                    "fused_lars expects contiguous cuda fp32 params and "
+                    "same-size grads");
+        TORCH_CHECK(!has_mu || (bufs[i].is_cuda() &&
+                                bufs[i].scalar_type() == at::kFloat &&
+                                bufs[i].is_contiguous() &&
+                                bufs[i].numel() == p.numel()),
+                    "fused_lars: momentum buffer must match its parameter");
+    }
+    long total = mt_total_chunks(params);
+    TORCH_CHECK(2 * total < (1L << 31), "multi-tensor list too large");
+    TORCH_CHECK(partials.is_cuda() && partials.scalar_type() == at::kFloat &&
+                partials.is_contiguous() && partials.numel() >= 2 * total,
+                "fused_lars: partials holds ", partials.numel(),
+                " floats, need ", 2 * total, " (two per chunk)");
+    TORCH_CHECK(ratios.is_cuda() && ratios.scalar_type() == at::kFloat &&
+                ratios.is_contiguous() &&
+                ratios.numel() >= (long)params.size(),
+                "fused_lars: ratios holds ", ratios.numel(),
+                " floats, need ", params.size(), " (one per tensor)");
+    float* pp = partials.data_ptr<float>();
+    float* rp = ratios.data_ptr<float>();
+    auto stream = at::hip::getCurrentHIPStream();
+    const float* fi = found_inf.has_value()
+        ? found_inf->data_ptr<float>() : nullptr;
+    const float* gs = nullptr;
+    if (grad_scale.has_value()) {
+        TORCH_CHECK(grad_scale->is_cuda() &&
+                    grad_scale->scalar_type() == at::kFloat &&
+                    grad_scale->numel() >= 1,
+                    "fused_lars: grad_scale must be a cuda fp32 tensor");
+        gs = grad_scale->data_ptr<float>();
+    }
+    int chunk_base = 0;
+    for (size_t start = 0; start < params.size(); start += MT_MAX) {
+        MTMeta m{};
+        int chunks = 0, nt = 0;
+        for (size_t i = start; i < std::min(params.size(), start + MT_MAX); ++i) {
+            m.a[nt] = grads[i].data_ptr<float>();
+            m.b[nt] = params[i].data_ptr<float>();
+            m.c[nt] = has_mu ? bufs[i].data_ptr<float>() : nullptr;
+            m.sizes[nt] = params[i].numel();
+            m.chunk_start[nt] = chunks;
+            chunks += ceil_div_i(params[i].numel(), MT_CHUNK);
+            ++nt;
+        }
+        m.chunk_start[nt] = chunks;
+        m.ntensors = nt;
+        if (chunks > 0) {
+            if (gs)
+                hipLaunchKernelGGL(k_mt_lars_sqsum<true>, dim3(chunks),
+                                   dim3(MT_BLOCK), 0, stream.stream(), m, fi,
+                                   gs, pp, chunk_base);
+            else
+                hipLaunchKernelGGL(k_mt_lars_sqsum<false>, dim3(chunks),
+                                   dim3(MT_BLOCK), 0, stream.stream(), m, fi,
+                                   gs, pp, chunk_base);
+            HIP_CHECK_LAST();
+        }
+        // also for a group of empty tensors: their ratios read 1
+        hipLaunchKernelGGL(k_mt_lars_ratio, dim3(nt), dim3(MT_BLOCK), 0,
+                           stream.stream(), m, pp, chunk_base, rp, (int)start,
+                           lr, wd, eta, eps, trust_clip ? 1 : 0, fi);
+        HIP_CHECK_LAST();
+        if (chunks == 0) continue;
+        if (gs)
+            hipLaunchKernelGGL(k_mt_lars<true>, dim3(chunks), dim3(MT_BLOCK),
+                               0, stream.stream(), m, (float)lr,
+                               (float)momentum, (float)wd, (float)nesterov,
+                               fi, gs, rp, (int)start);
+        else
+            hipLaunchKernelGGL(k_mt_lars<false>, dim3(chunks), dim3(MT_BLOCK),
+                               0, stream.stream(), m, (float)lr,
+                               (float)momentum, (float)wd, (float)nesterov,
+                               fi, gs, rp, (int)start);
+        HIP_CHECK_LAST();
+        chunk_base += chunks;
     }
 }
 

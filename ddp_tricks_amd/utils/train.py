@@ -24,7 +24,7 @@ from torch.utils.data import DataLoader
 
 from .. import amp
 from ..models import build_model
-from ..ops.optim import FusedSGD
+from ..ops.optim import FusedLARS, FusedSGD, lars_param_groups
 from ..parallel.ddp import DistributedDataParallel as DDP
 from .callbacks import EarlyStopping, same_seeds
 from .data import (DATASETS, Augment, CudaPrefetcher, DeviceBatchLoader,
@@ -155,8 +155,25 @@ def train(args):
 
     os.makedirs(os.path.join(args.model_path, "logs"), exist_ok=True)
     latest_model_path = os.path.join(args.model_path, args.exp_name)
-    optimizer = FusedSGD(model.parameters(), lr=args.learning_rate,
-                         momentum=0.9, nesterov=True)
+    # --optimizer / --weight_decay / --lars_eta (extension); the defaults
+    # build the reference's SGD(lr, momentum=0.9, nesterov=True)
+    optimizer_name = getattr(args, "optimizer", None) or "sgd"
+    weight_decay = float(getattr(args, "weight_decay", 0.0) or 0.0)
+    if weight_decay < 0.0:
+        raise ValueError("--weight_decay must be >= 0")
+    if optimizer_name == "sgd":
+        optimizer = FusedSGD(model.parameters(), lr=args.learning_rate,
+                             momentum=0.9, weight_decay=weight_decay,
+                             nesterov=True)
+    elif optimizer_name == "lars":
+        # layer-wise trust ratios on the weights; BN scale/shift and biases
+        # take the plain SGD step without decay
+        lars_eta = float(getattr(args, "lars_eta", None) or 0.001)
+        optimizer = FusedLARS(lars_param_groups(model, weight_decay),
+                              lr=args.learning_rate, momentum=0.9,
+                              nesterov=True, trust_coefficient=lars_eta)
+    else:
+        raise ValueError(f"unknown optimizer {optimizer_name!r}")
     lookahead = Lookahead(optimizer=optimizer, k=10, alpha=0.5)
     from ..ops.functional import cross_entropy_loss as loss_function
     # --label_smoothing binds into the TRAINING loss only; validation keeps

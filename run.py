@@ -72,6 +72,16 @@ def parse_args():
                         help="per-sample CutMix probability on the train "
                              "loader (alpha = 1 boxes); implies "
                              "--device_data on GPU")
+    parser.add_argument("--optimizer", default="sgd", type=str,
+                        choices=("sgd", "lars"),
+                        help="sgd: fused nesterov SGD; lars: the same step "
+                             "with layer-wise trust ratios on the weights "
+                             "(BN parameters and biases are not adapted)")
+    parser.add_argument("--weight_decay", default=0.0, type=float,
+                        help="L2 weight decay (with --optimizer lars: on the "
+                             "adapted tensors only)")
+    parser.add_argument("--lars_eta", default=0.001, type=float,
+                        help="LARS trust coefficient")
     args = parser.parse_args()
     if args.local_rank is None:
         args.local_rank = int(os.environ.get("LOCAL_RANK", 0))
