@@ -18,5 +18,17 @@ def build_model(name: str, **kwargs):
         raise ValueError(f"unknown model {name!r}; available: {sorted(_REGISTRY)}")
 
 
+def model_accepts(name: str, kwarg: str) -> bool:
+    """Whether the registered constructor takes ``kwarg`` by name."""
+    import inspect
+    try:
+        ctor = _REGISTRY[name]
+    except KeyError:
+        raise ValueError(f"unknown model {name!r}; available: {sorted(_REGISTRY)}")
+    params = inspect.signature(ctor).parameters
+    return kwarg in params or any(
+        p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values())
+
+
 def register_model(name: str, ctor) -> None:
     _REGISTRY[name] = ctor

@@ -10,6 +10,11 @@ epilogues, 2×2 maxpool on the dedicated kernel.
 ``cifar_head=True`` shrinks the classifier for 32×32 inputs
 (512·1·1 → 512 hidden), mirroring common CIFAR-VGG practice.
 
+``dropout > 0`` turns the classifier's two dropout slots into counter-hash
+``ops.Dropout`` modules and runs each Linear → ReLU → Dropout junction as
+one fused op (``linear_relu_dropout``); the default ``0.0`` keeps the inert
+``nn.Dropout`` slots and the plain forward.
+
 State-dict layout follows torchvision's vgg16_bn naming
 (features.N.weight / classifier.N.weight) so torchvision-trained
 checkpoints map by key.
@@ -19,8 +24,8 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from ..ops.functional import conv_bn
-from ..ops.modules import (BatchNorm2d, Conv2d, Flatten, Identity,
+from ..ops.functional import conv_bn, linear_relu_dropout
+from ..ops.modules import (BatchNorm2d, Conv2d, Dropout, Flatten, Identity,
                            Linear, MaxPool2d)
 
 # vgg16 plan: channel widths with 'M' = 2x2/2 maxpool
@@ -45,13 +50,20 @@ class VGG16BN(nn.Module):
         self.features = nn.Sequential(*layers)
         feat = 512 if cifar_head else 512 * 7 * 7
         hidden = 512 if cifar_head else 4096
+        # dropout > 0: counter-hash Dropout slots, fused with the Linear and
+        # the ReLU in front of them (forward); 0.0 keeps the inert nn.Dropout
+        self.fused_dropout = dropout > 0
+
+        def drop():
+            return Dropout(p=dropout) if self.fused_dropout \
+                else nn.Dropout(p=dropout)
         self.classifier = nn.Sequential(
             Linear(feat, hidden),
             Identity(),                     # ReLU (applied in forward)
-            nn.Dropout(p=dropout),
+            drop(),
             Linear(hidden, hidden),
             Identity(),
-            nn.Dropout(p=dropout),
+            drop(),
             Linear(hidden, num_classes),
         )
         self.flatten = Flatten()   # NHWC-aware at the conv->dense junction
@@ -86,6 +98,12 @@ class VGG16BN(nn.Module):
                 i += 1
         x = self.flatten(x)
         c = self.classifier
+        if self.fused_dropout:
+            # Linear -> ReLU -> Dropout junctions as one op each (training:
+            # ReLU + mask in the GEMM epilogue; eval: ReLU alone)
+            x = linear_relu_dropout(c[0], c[2], x)
+            x = linear_relu_dropout(c[3], c[5], x)
+            return c[6](x)
         x = torch.relu(c[0](x))
         x = c[2](x)
         x = torch.relu(c[3](x))

@@ -112,5 +112,7 @@ def require_ext_for(tensor):
 from .functional import (  # noqa: E402,F401
     conv2d, linear, batch_norm, max_pool2d, relu, cross_entropy_loss,
     clip_grad_norm_, sync_batch_norm, MixedTarget,
+    dropout, dropout_rng, linear_relu_dropout,
 )
+from .modules import Dropout  # noqa: E402,F401
 from .optim import FusedSGD, FusedLARS, lars_param_groups  # noqa: E402,F401

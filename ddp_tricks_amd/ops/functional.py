@@ -12,8 +12,10 @@ ops in fp32, doubling as the numerics oracle the GPU tests compare against.
 """
 from __future__ import annotations
 
+import math
 import os
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -368,6 +370,234 @@ def linear(x, weight, bias=None):
         return F.linear(_to_bf16(x), bf16_weight(weight),
                         bias.to(torch.bfloat16) if bias is not None else None)
     return F.linear(x, weight, bias)
+
+
+# ---------------------------------------------------------------- dropout ---
+#
+# Counter-hash dropout: the mask is a pure function of (seed, rank, epoch,
+# call number, element offset) — layout in ops/hip/common.h — so it is the
+# same on CPU and GPU, needs no stored mask tensor and is reproduced by a
+# resumed run (the call counter restarts with every epoch).
+
+_U64 = (1 << 64) - 1
+# seed salts of the dropout stream (ops/hip/common.h, dropout header)
+DROP_SALT = 0xA0761D6478BD642F
+DROP_RANK_SALT = 0xE7037ED1A0B428DB
+
+
+def _drop_hash(s: int, key: int) -> int:
+    """``h(s, key)`` of the kernels, in Python integers modulo 2^64."""
+    z = (s + (key + 1) * 0x9E3779B97F4A7C15) & _U64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _U64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _U64
+    return z ^ (z >> 31)
+
+
+def dropout_threshold(p: float) -> int:
+    """Drop probability as the kernels' 16-bit threshold
+    ``floor(p*65536 + 0.5)``: an element is dropped when its 16 hashed bits
+    are below it, so the effective probability is ``thr/65536``.  ``p < 0``
+    and a ``p`` that rounds to 65536 (everything dropped) are refused."""
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"dropout probability must be in [0, 1), got {p}")
+    thr = int(math.floor(p * 65536.0 + 0.5))
+    if thr > 65535:
+        raise ValueError(
+            f"dropout probability {p} rounds to 1 (threshold {thr} > 65535)")
+    return thr
+
+
+def dropout_scale(thr: int) -> float:
+    """``float32(65536 / (65536 - thr))``, the kept elements' factor (exactly
+    1 for ``thr == 0``)."""
+    return float(np.float32(65536.0 / (65536.0 - thr)))
+
+
+def dropout_mask(call_seed: int, numel: int, thr: int) -> np.ndarray:
+    """The numpy mirror of the kernels' mask: bool [numel], True where
+    element ``i`` (offset in the output's dense storage) is KEPT."""
+    u = np.uint64
+    i = np.arange(int(numel), dtype=np.uint64)
+    s = np.full(1, int(call_seed) & _U64, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        z = s + ((i >> u(2)) + u(1)) * u(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> u(30))) * u(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> u(27))) * u(0x94D049BB133111EB)
+    z = z ^ (z >> u(31))
+    lane = (z >> (u(16) * (i & u(3)))) & u(0xFFFF)
+    return lane >= u(int(thr))
+
+
+class DropoutRNG:
+    """Host side of the dropout stream: hands one 64-bit ``call_seed`` to
+    every dropout call in training,
+
+        call_seed = h(seed ^ DROP_SALT ^ rank*DROP_RANK_SALT,
+                      (epoch << 32) | calls)
+
+    in Python integers — no tensor, no H2D copy, no sync.  ``set_epoch``
+    restarts the call counter, so a run resumed at an epoch boundary draws
+    the masks the uninterrupted run would have."""
+
+    def __init__(self):
+        self._seed = 0
+        self.rank = 0
+        self.epoch = 0
+        self.calls = 0
+
+    def seed(self, seed: int, rank=None) -> None:
+        """Key the stream; ``rank`` defaults to the initialised process
+        group's rank, else 0.  Restarts epoch 0, call 0."""
+        if rank is None:
+            import torch.distributed as dist
+            rank = dist.get_rank() if (dist.is_available()
+                                       and dist.is_initialized()) else 0
+        self._seed = int(seed) & _U64
+        self.rank = int(rank)
+        self.epoch = 0
+        self.calls = 0
+
+    def set_epoch(self, epoch: int) -> None:
+        self.epoch = int(epoch)
+        self.calls = 0
+
+    def next_call_seed(self) -> int:
+        base = (self._seed ^ DROP_SALT
+                ^ (self.rank * DROP_RANK_SALT)) & _U64
+        key = ((self.epoch << 32) | (self.calls & 0xFFFFFFFF)) & _U64
+        self.calls += 1
+        return _drop_hash(base, key)
+
+    def state_dict(self) -> dict:
+        return {"seed": self._seed, "rank": self.rank, "epoch": self.epoch,
+                "calls": self.calls}
+
+    def load_state_dict(self, sd: dict) -> None:
+        self._seed = int(sd["seed"]) & _U64
+        self.rank = int(sd["rank"])
+        self.epoch = int(sd["epoch"])
+        self.calls = int(sd["calls"])
+
+
+dropout_rng = DropoutRNG()
+
+
+def _seed_i64(call_seed: int) -> int:
+    """The bindings take the 64 seed bits as int64."""
+    return call_seed - (1 << 64) if call_seed >> 63 else call_seed
+
+
+def _storage_mask(call_seed: int, thr: int, like: torch.Tensor):
+    """``dropout_mask`` laid out over ``like`` (a dense contiguous or
+    channels_last tensor), indexed in storage order."""
+    m = torch.from_numpy(dropout_mask(call_seed, like.numel(), thr))
+    m = m.to(like.device)
+    if like.is_contiguous():
+        return m.view(like.shape)
+    N, C, H, W = like.shape
+    return m.view(N, H, W, C).permute(0, 3, 1, 2)
+
+
+def _dense(x: torch.Tensor) -> torch.Tensor:
+    if x.is_contiguous() or (x.dim() == 4
+                             and x.is_contiguous(memory_format=CL)):
+        return x
+    return x.contiguous()
+
+
+def _torch_drop(v: torch.Tensor, call_seed: int, thr: int) -> torch.Tensor:
+    """The kernels' formula in torch: v*scale (rounded to v's dtype) where
+    kept, +0 where dropped."""
+    scale = dropout_scale(thr)
+    keep = _storage_mask(call_seed, thr, v)
+    scaled = (v.float() * scale).to(v.dtype) if v.dtype != torch.float64 \
+        else v * scale
+    return torch.where(keep, scaled, torch.zeros_like(scaled))
+
+
+class _HIPDropout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, thr, scale, call_seed):
+        ext = require_ext_for(x)
+        xd = _dense(x)
+        ctx.meta = (thr, scale, call_seed, not xd.is_contiguous())
+        return ext.dropout_fwd(xd, thr, scale, call_seed)
+
+    @staticmethod
+    def backward(ctx, dy):
+        thr, scale, call_seed, chlast = ctx.meta
+        ext = require_ext_for(dy)
+        # dy takes the forward's layout: the mask is indexed by storage offset
+        dy = dy.contiguous(memory_format=CL) if chlast else dy.contiguous()
+        return ext.dropout_bwd(dy, thr, scale, call_seed), None, None, None
+
+
+def dropout(x, p: float = 0.5, training: bool = True):
+    """Counter-hash dropout.  In eval mode, or when ``p`` rounds to a zero
+    threshold, returns ``x`` itself with no launch and no draw from
+    ``dropout_rng``."""
+    thr = dropout_threshold(p) if training else 0
+    if thr == 0:
+        return x
+    call_seed = dropout_rng.next_call_seed()
+    if x.is_cuda and require_ext_for(x) is not None:
+        if x.dtype not in (torch.bfloat16, torch.float32):
+            raise TypeError(f"HIP dropout takes bf16 or fp32, got {x.dtype}")
+        return _HIPDropout.apply(x, thr, dropout_scale(thr),
+                                 _seed_i64(call_seed))
+    return _torch_drop(_dense(x), call_seed, thr)
+
+
+class _HIPLinearAct(torch.autograd.Function):
+    """dropout(relu(linear(x))) with the ReLU and the mask in the GEMM
+    epilogue.  Saves xb, wb and the output y; the backward reads the mask
+    off y (y > 0 iff kept and active, as scale >= 1)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, thr, scale, call_seed):
+        ext = require_ext_for(x)
+        xb = _to_bf16(x.contiguous())
+        wb = weight_variant(weight, "flat")
+        bias_f = bias if bias is None else bias.detach().float()
+        y = ext.linear_act_fwd(xb, wb, bias_f, thr, scale, call_seed)
+        ctx.save_for_backward(xb, wb, y)
+        ctx.meta = (x.dtype, bias is not None, scale)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xb, wb, y = ctx.saved_tensors
+        x_dtype, has_bias, scale = ctx.meta
+        ext = require_ext_for(dy)
+        dz = ext.relu_drop_bwd(_to_bf16(dy.contiguous()), y, scale)
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = ext.linear_dgrad(dz, wb)
+            if x_dtype == torch.float32:
+                dx = dx.float()
+        if ctx.needs_input_grad[1]:
+            dw = ext.linear_wgrad(dz, xb)
+        if has_bias and ctx.needs_input_grad[2]:
+            db = ext.col_sum(dz)
+        return dx, dw, db, None, None, None
+
+
+def linear_relu_dropout(lin_mod, drop_mod, x):
+    """The Linear -> ReLU -> Dropout junction as one op.  GPU: one GEMM
+    with the fused epilogue (training: ReLU + dropout; eval or ``p`` that
+    rounds to 0: ReLU alone, no draw from ``dropout_rng``).  CPU: the same
+    formula in torch with the mirror's mask, so a CPU model and a GPU model
+    draw identical masks."""
+    thr = dropout_threshold(drop_mod.p) if drop_mod.training else 0
+    call_seed = dropout_rng.next_call_seed() if thr else 0
+    if x.is_cuda and require_ext_for(x) is not None:
+        return _HIPLinearAct.apply(x, lin_mod.weight, lin_mod.bias, thr,
+                                   dropout_scale(thr), _seed_i64(call_seed))
+    y = torch.relu(linear(x, lin_mod.weight, lin_mod.bias))
+    if thr == 0:
+        return y
+    return _torch_drop(y.contiguous(), call_seed, thr)
 
 
 # ------------------------------------------------------------- batch norm ---

@@ -30,6 +30,10 @@ at::Tensor nhwc_flatten(at::Tensor x);
 at::Tensor nhwc_unflatten(at::Tensor dy, long C, long H, long W);
 std::vector<at::Tensor> pack_conv_weight(at::Tensor w, bool pad8,
                                          bool want_wt2);
+at::Tensor dropout_fwd(at::Tensor x, long thr, double scale, long call_seed);
+at::Tensor dropout_bwd(at::Tensor dy, long thr, double scale, long call_seed);
+at::Tensor relu_dropout_fwd(at::Tensor x, long thr, double scale,
+                            long call_seed);
 
 // ce.hip
 std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor target);
@@ -108,6 +112,10 @@ at::Tensor col_sum(at::Tensor x);
 at::Tensor linear_fwd(at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias);
 at::Tensor linear_dgrad(at::Tensor dy, at::Tensor w);
 at::Tensor linear_wgrad(at::Tensor dy, at::Tensor x);
+at::Tensor linear_act_fwd(at::Tensor x, at::Tensor w,
+                          c10::optional<at::Tensor> bias, long thr,
+                          double scale, long call_seed);
+at::Tensor relu_drop_bwd(at::Tensor dy, at::Tensor y, double scale);
 
 // conv.hip
 at::Tensor conv2d_fwd(at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias,
@@ -268,6 +276,28 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("bias") = c10::nullopt);
     m.def("linear_dgrad", &linear_dgrad);
     m.def("linear_wgrad", &linear_wgrad);
+    m.def("linear_act_fwd", &linear_act_fwd,
+          "bf16 dropout(relu(x w^T + bias)) in the GEMM epilogue; thr is the "
+          "drop probability in 1/65536 (0: ReLU alone), scale = "
+          "65536/(65536-thr), call_seed the per-call seed's 64 bits as int64",
+          py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("thr"),
+          py::arg("scale"), py::arg("call_seed"));
+    m.def("relu_drop_bwd", &relu_drop_bwd,
+          "dz = dy*scale where the fused forward's output y > 0, else 0",
+          py::arg("dy"), py::arg("y"), py::arg("scale"));
+    m.def("dropout_fwd", &dropout_fwd,
+          "counter-hash dropout in storage order (bf16/fp32, contiguous or "
+          "channels_last)",
+          py::arg("x"), py::arg("thr"), py::arg("scale"),
+          py::arg("call_seed"));
+    m.def("dropout_bwd", &dropout_bwd,
+          "dropout backward: the same mask, regenerated, applied to dy",
+          py::arg("dy"), py::arg("thr"), py::arg("scale"),
+          py::arg("call_seed"));
+    m.def("relu_dropout_fwd", &relu_dropout_fwd,
+          "dropout_fwd over relu(x)",
+          py::arg("x"), py::arg("thr"), py::arg("scale"),
+          py::arg("call_seed"));
     m.def("conv2d_fwd", &conv2d_fwd, py::arg("x"), py::arg("w"),
           py::arg("bias") = c10::nullopt, py::arg("stride") = 1,
           py::arg("pad") = 0, py::arg("kwalk") = -1);

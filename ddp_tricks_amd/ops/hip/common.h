@@ -110,7 +110,42 @@ DEV_INLINE unsigned fd_mod(unsigned n, FastDiv f, unsigned q) {
     return n - q * f.d;
 }
 
-#define HIP_CHECK_LAST()                                                     \
+// Counter-hash dropout (gemm.hip epilogues, elementwise.hip standalone
+// kernels; numpy mirror ops/functional.py dropout_mask).  The mask is a pure
+// function of (call_seed, element offset in the output's dense storage):
+//
+//   h(s, key) = fin(s + (key + 1) * 0x9E3779B97F4A7C15)      (data.hip's hash)
+//   fin(z):  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+//            z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+//            z =  z ^ (z >> 31)
+//   z    = h(call_seed, i >> 2)              one hash per 4 elements
+//   lane = (z >> 16*(i & 3)) & 0xFFFF
+//   keep = lane >= thr                       thr = floor(p*65536 + 0.5)
+//
+// call_seed comes from the host (ops.functional.DropoutRNG), one per call:
+//   call_seed = h(seed ^ DROP_SALT ^ rank*DROP_RANK_SALT,
+//                 (epoch << 32) | calls)
+//   DROP_SALT      = 0xA0761D6478BD642F
+//   DROP_RANK_SALT = 0xE7037ED1A0B428DB
+// Kept values are scaled by scale = float(65536 / (65536 - thr)), a kernel
+// argument; thr == 0 does no hashing.
+DEV_INLINE unsigned long long drop_hash(unsigned long long s,
+                                        unsigned long long key) {
+    unsigned long long z = s + (key + 1ull) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+// 16 mask bits of element i out of its group's hash z
+DEV_INLINE unsigned drop_lane(unsigned long long z, unsigned i) {
+    return (unsigned)(z >> (16u * (i & 3u))) & 0xFFFFu;
+}
+DEV_INLINE bool drop_keep(unsigned long long call_seed, long i, unsigned thr) {
+    return drop_lane(drop_hash(call_seed, (unsigned long long)i >> 2),
+                     (unsigned)i) >= thr;
+}
+
+#define HIP_CHECK_LAST()                                                    \
     do {                                                                     \
         hipError_t e = hipGetLastError();                                    \
         if (e != hipSuccess) {                                               \

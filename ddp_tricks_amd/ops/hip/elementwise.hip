@@ -737,6 +737,142 @@ void fused_lookahead(std::vector<at::Tensor> fast, std::vector<at::Tensor> slow,
     }
 }
 
+// ----------------------------------------------------------------- dropout ---
+
+// Standalone counter-hash dropout (mask contract: common.h), for layers that
+// are not a Linear+ReLU junction (those fuse it into the GEMM epilogue).
+//   y[i] = round(x[i] * scale) where element i is kept, +0 where dropped,
+// i the offset in the tensor's dense storage (contiguous or channels_last
+// alike).  RELU applies relu first (the N <= 16 linear_act composition).
+// The backward is the same map on dy: it REGENERATES the bits, because
+// y == 0 says nothing about the mask here.  thr == 0 does no hashing.
+// Eight elements and two hashes per thread; scalar tail, one hash each.
+DEV_INLINE float drop_value(float v, bool relu, bool keep, float scale) {
+    if (relu) v = v <= 0.f ? 0.f : v;      // NaN passes, -0 -> +0
+    return keep ? __fmul_rn(v, scale) : 0.f;
+}
+
+template <bool RELU>
+__global__ void k_dropout_bf16(const unsigned short* __restrict__ x,
+                               unsigned short* __restrict__ y, long n,
+                               unsigned thr, float scale,
+                               unsigned long long seed, int aligned) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    long stride = (long)gridDim.x * blockDim.x;
+    long nv = aligned ? (n >> 3) : 0;
+    for (long v = i; v < nv; v += stride) {
+        s16x8 a = reinterpret_cast<const s16x8*>(x)[v];
+        unsigned long long z0 = 0, z1 = 0;
+        if (thr != 0) {
+            z0 = drop_hash(seed, (unsigned long long)v * 2);
+            z1 = drop_hash(seed, (unsigned long long)v * 2 + 1);
+        }
+        s16x8 o;
+        #pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            bool keep = thr == 0 ||
+                drop_lane(j < 4 ? z0 : z1, (unsigned)j) >= thr;
+            o[j] = (short)f2us(drop_value(us2f((unsigned short)a[j]), RELU,
+                                          keep, scale));
+        }
+        reinterpret_cast<s16x8*>(y)[v] = o;
+    }
+    for (long j = nv * 8 + i; j < n; j += stride) {
+        bool keep = thr == 0 || drop_keep(seed, j, thr);
+        y[j] = f2us(drop_value(us2f(x[j]), RELU, keep, scale));
+    }
+}
+
+template <bool RELU>
+__global__ void k_dropout_f32(const float* __restrict__ x,
+                              float* __restrict__ y, long n, unsigned thr,
+                              float scale, unsigned long long seed,
+                              int aligned) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    long stride = (long)gridDim.x * blockDim.x;
+    long nv = aligned ? (n >> 3) : 0;
+    for (long v = i; v < nv; v += stride) {
+        #pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            f32x4 a = reinterpret_cast<const f32x4*>(x)[v * 2 + h];
+            unsigned long long z = 0;
+            if (thr != 0) z = drop_hash(seed, (unsigned long long)v * 2 + h);
+            #pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                bool keep = thr == 0 || drop_lane(z, (unsigned)j) >= thr;
+                a[j] = drop_value(a[j], RELU, keep, scale);
+            }
+            reinterpret_cast<f32x4*>(y)[v * 2 + h] = a;
+        }
+    }
+    for (long j = nv * 8 + i; j < n; j += stride) {
+        bool keep = thr == 0 || drop_keep(seed, j, thr);
+        y[j] = drop_value(x[j], RELU, keep, scale);
+    }
+}
+
+static at::Tensor launch_dropout(const at::Tensor& x, long thr, double scale,
+                                 long call_seed, bool relu) {
+    TORCH_CHECK(thr >= 0 && thr <= 65535, "dropout threshold ", thr,
+                " outside [0, 65535]");
+    TORCH_CHECK(thr != 0 || scale == 1.0, "thr == 0 needs scale == 1");
+    TORCH_CHECK(x.is_cuda() && (x.scalar_type() == at::kBFloat16 ||
+                                x.scalar_type() == at::kFloat),
+                "dropout: cuda bf16 or fp32 expected");
+    // dense storage, indexed in storage order
+    TORCH_CHECK(x.is_contiguous() ||
+                (x.dim() == 4 &&
+                 x.is_contiguous(at::MemoryFormat::ChannelsLast)),
+                "dropout: contiguous or channels_last tensor expected");
+    auto y = at::empty_like(x);     // keeps x's strides
+    long n = x.numel();
+    if (n == 0) return y;
+    int aligned = (((uintptr_t)x.data_ptr() | (uintptr_t)y.data_ptr()) & 15)
+                  == 0;
+    int blocks = (int)std::min<long>(4096, ceil_div_i(ceil_div_i(n, 8), 256));
+    auto stream = at::hip::getCurrentHIPStream();
+    unsigned long long seed = (unsigned long long)call_seed;
+    if (x.scalar_type() == at::kBFloat16) {
+        auto xp = reinterpret_cast<const unsigned short*>(x.data_ptr());
+        auto yp = reinterpret_cast<unsigned short*>(y.data_ptr());
+        if (relu)
+            hipLaunchKernelGGL(k_dropout_bf16<true>, dim3(blocks), dim3(256),
+                               0, stream.stream(), xp, yp, n, (unsigned)thr,
+                               (float)scale, seed, aligned);
+        else
+            hipLaunchKernelGGL(k_dropout_bf16<false>, dim3(blocks), dim3(256),
+                               0, stream.stream(), xp, yp, n, (unsigned)thr,
+                               (float)scale, seed, aligned);
+    } else {
+        if (relu)
+            hipLaunchKernelGGL(k_dropout_f32<true>, dim3(blocks), dim3(256),
+                               0, stream.stream(), x.data_ptr<float>(),
+                               y.data_ptr<float>(), n, (unsigned)thr,
+                               (float)scale, seed, aligned);
+        else
+            hipLaunchKernelGGL(k_dropout_f32<false>, dim3(blocks), dim3(256),
+                               0, stream.stream(), x.data_ptr<float>(),
+                               y.data_ptr<float>(), n, (unsigned)thr,
+                               (float)scale, seed, aligned);
+    }
+    HIP_CHECK_LAST();
+    return y;
+}
+
+at::Tensor dropout_fwd(at::Tensor x, long thr, double scale, long call_seed) {
+    return launch_dropout(x, thr, scale, call_seed, false);
+}
+
+at::Tensor dropout_bwd(at::Tensor dy, long thr, double scale,
+                       long call_seed) {
+    return launch_dropout(dy, thr, scale, call_seed, false);
+}
+
+at::Tensor relu_dropout_fwd(at::Tensor x, long thr, double scale,
+                            long call_seed) {
+    return launch_dropout(x, thr, scale, call_seed, true);
+}
+
 // ------------------------------------------------------------------- casts ---
 
 __global__ void k_f32_to_bf16(const float* __restrict__ in,

@@ -13,6 +13,15 @@
 // distinct multiples of 4 — see cdna_hip_programming.md §6 Guideline 4).
 // Split-K (grid.z) writes fp32 partial slabs, combined by a deterministic
 // fixed-order reduction (no fp atomics anywhere).
+//
+// Epilogue modes (bf16 output only): EPI_RELU writes relu(acc + bias),
+// EPI_RELU_DROP writes relu(acc + bias) * scale where the counter-hash mask
+// (common.h) keeps the element and +0 where it drops it.  The mask is
+// evaluated from the element's offset row*N + col and never stored; with
+// split-K the epilogue runs in the combine kernel.  The per-call seed is
+// the host's h(seed ^ DROP_SALT ^ rank*DROP_RANK_SALT, (epoch << 32) | calls)
+// with DROP_SALT = 0xA0761D6478BD642F, DROP_RANK_SALT = 0xE7037ED1A0B428DB
+// (mirror: ops/functional.py).
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -24,13 +33,26 @@ constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int LDK = BK + 8;          // padded row length (bf16 elements)
 constexpr int GEMM_THREADS = 256;
 
+enum { EPI_NONE = 0, EPI_RELU = 1, EPI_RELU_DROP = 2 };
+
+struct DropArgs {
+    unsigned long long seed;   // per-call seed
+    unsigned thr;              // drop when the 16 hashed bits are < thr
+    float scale;               // 65536 / (65536 - thr)
+};
+
+// relu with NaN passed through and -0 -> +0
+DEV_INLINE float relu_pos(float v) { return v <= 0.f ? 0.f : v; }
+
 // ------------------------------------------------------------ core kernel ---
 
-template <bool OUT_F32, bool SPLITK>
+template <bool OUT_F32, bool SPLITK, int EPI = EPI_NONE>
 __global__ __launch_bounds__(GEMM_THREADS)
 void k_gemm_tn(const bf16* __restrict__ A, const bf16* __restrict__ B,
                const float* __restrict__ bias, void* __restrict__ Cout,
-               int M, int N, int K, int k_per_split) {
+               int M, int N, int K, int k_per_split, DropArgs drop) {
+    static_assert(EPI == EPI_NONE || (!OUT_F32 && !SPLITK),
+                  "epilogue modes write the final bf16 tile");
     __shared__ bf16 lds_a[BM][LDK];
     __shared__ bf16 lds_b[BN][LDK];
 
@@ -119,6 +141,11 @@ void k_gemm_tn(const bf16* __restrict__ A, const bf16* __restrict__ B,
                 int row = m0 + wr * 64 + mi * 16 + (lane >> 4) * 4 + r;
                 if (row >= M) continue;
                 float v = acc[mi][ni][r] + badd;
+                if (EPI != EPI_NONE) v = relu_pos(v);
+                if (EPI == EPI_RELU_DROP) {
+                    v = drop_keep(drop.seed, (long)row * N + col, drop.thr)
+                        ? __fmul_rn(v, drop.scale) : 0.f;
+                }
                 if (SPLITK) {
                     float* slab = reinterpret_cast<float*>(Cout);
                     slab[((long)blockIdx.z * M + row) * N + col] = v;
@@ -134,18 +161,45 @@ void k_gemm_tn(const bf16* __restrict__ A, const bf16* __restrict__ B,
 }
 
 // deterministic split-K combine: out[i] = bias-free fixed-order sum of slabs
-template <bool OUT_F32>
+// (+ bias).  The epilogue modes walk groups of four consecutive elements so
+// one hash serves its whole group.
+template <bool OUT_F32, int EPI = EPI_NONE>
 __global__ void k_splitk_combine(const float* __restrict__ slab, int S,
                                  long MN, int N, const float* __restrict__ bias,
-                                 void* __restrict__ out) {
+                                 void* __restrict__ out, DropArgs drop) {
+    static_assert(EPI == EPI_NONE || !OUT_F32, "epilogue modes write bf16");
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     long stride = (long)gridDim.x * blockDim.x;
-    for (; i < MN; i += stride) {
-        float v = 0.f;
-        for (int s = 0; s < S; ++s) v += slab[(long)s * MN + i];
-        if (bias) v += bias[i % N];
-        if (OUT_F32) reinterpret_cast<float*>(out)[i] = v;
-        else reinterpret_cast<bf16*>(out)[i] = f2bf(v);
+    if (EPI == EPI_NONE) {
+        for (; i < MN; i += stride) {
+            float v = 0.f;
+            for (int s = 0; s < S; ++s) v += slab[(long)s * MN + i];
+            if (bias) v += bias[i % N];
+            if (OUT_F32) reinterpret_cast<float*>(out)[i] = v;
+            else reinterpret_cast<bf16*>(out)[i] = f2bf(v);
+        }
+        return;
+    }
+    const long groups = (MN + 3) >> 2;
+    for (long g = i; g < groups; g += stride) {
+        unsigned long long z = 0;
+        if (EPI == EPI_RELU_DROP) z = drop_hash(drop.seed, (unsigned long long)g);
+        const long e0 = g << 2;
+        int col = (int)(e0 % N);
+        #pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long e = e0 + j;
+            if (e >= MN) break;
+            float v = 0.f;
+            for (int s = 0; s < S; ++s) v += slab[(long)s * MN + e];
+            if (bias) v += bias[col];
+            if (++col == N) col = 0;
+            v = relu_pos(v);
+            if (EPI == EPI_RELU_DROP)
+                v = drop_lane(z, (unsigned)j) >= drop.thr
+                    ? __fmul_rn(v, drop.scale) : 0.f;
+            reinterpret_cast<bf16*>(out)[e] = f2bf(v);
+        }
     }
 }
 
@@ -313,51 +367,119 @@ __global__ void k_colsum_combine(const float* __restrict__ slab, int S, int C,
     if (lane == 0) out[c] = v;
 }
 
+// --------------------------------------------------- relu+dropout backward ---
+
+// dz = bf16(float(dy) * scale) where y > 0, else +0.  y is the fused
+// forward's output: scale >= 1, so y > 0 exactly where the element was kept
+// and its pre-activation was positive; no mask is read or regenerated.
+// aligned: both pointers 16-byte aligned (s16x8 body), else all scalar.
+__global__ void k_relu_drop_bwd(const bf16* __restrict__ dy,
+                                const bf16* __restrict__ y,
+                                bf16* __restrict__ dz, long n, float scale,
+                                int aligned) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    long stride = (long)gridDim.x * blockDim.x;
+    long nv = aligned ? (n >> 3) : 0;
+    for (long v = i; v < nv; v += stride) {
+        s16x8 g = reinterpret_cast<const s16x8*>(dy)[v];
+        s16x8 a = reinterpret_cast<const s16x8*>(y)[v];
+        s16x8 o;
+        #pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            float d = __fmul_rn(us2f((unsigned short)g[j]), scale);
+            o[j] = us2f((unsigned short)a[j]) > 0.f ? (short)f2us(d) : (short)0;
+        }
+        reinterpret_cast<s16x8*>(dz)[v] = o;
+    }
+    for (long j = nv * 8 + i; j < n; j += stride) {
+        float d = __fmul_rn(bf2f(dy[j]), scale);
+        dz[j] = bf2f(y[j]) > 0.f ? f2bf(d) : f2bf(0.f);
+    }
+}
+
 // ------------------------------------------------------------------ hosts ---
 
+// split-K when the tile grid underfills the 256-CU chip; returns the number
+// of splits and the BK-aligned K range of each
+static int splitk_plan(int gm, int gn, int K, int& k_per_split) {
+    int S = 1;
+    while (gm * gn * S < 512 && S < 16 && (K / (S * 2)) >= BK) S *= 2;
+    k_per_split = K;
+    if (S > 1) {
+        k_per_split = ceil_div_i(K, S);
+        k_per_split = ((k_per_split + BK - 1) / BK) * BK;
+        S = ceil_div_i(K, k_per_split);  // recompute actual
+    }
+    return S;
+}
+
+// epi: EPI_NONE for every plain product; the ReLU / ReLU+dropout modes are
+// linear_act_fwd's and need a bf16 C
 static void launch_gemm_tn(const at::Tensor& A, const at::Tensor& B,
                            const c10::optional<at::Tensor>& bias,
-                           at::Tensor& C, bool out_f32) {
+                           at::Tensor& C, bool out_f32, int epi = EPI_NONE,
+                           DropArgs drop = DropArgs{0ull, 0u, 1.0f}) {
     int M = A.size(0), K = A.size(1), N = B.size(0);
     auto stream = at::hip::getCurrentHIPStream();
     const bf16* a = reinterpret_cast<const bf16*>(A.data_ptr());
     const bf16* b = reinterpret_cast<const bf16*>(B.data_ptr());
     const float* bp = bias.has_value() ? bias->data_ptr<float>() : nullptr;
+    TORCH_CHECK(epi == EPI_NONE || !out_f32);
 
     int gm = ceil_div_i(M, BM), gn = ceil_div_i(N, BN);
-    // split-K when the tile grid underfills the 256-CU chip
-    int S = 1;
-    while (gm * gn * S < 512 && S < 16 && (K / (S * 2)) >= BK) S *= 2;
+    int k_per_split;
+    int S = splitk_plan(gm, gn, K, k_per_split);
     if (S > 1) {
-        int k_per_split = ceil_div_i(K, S);
-        k_per_split = ((k_per_split + BK - 1) / BK) * BK;
-        S = ceil_div_i(K, k_per_split);  // recompute actual
         auto slab = at::empty({S, M, N}, A.options().dtype(at::kFloat));
         hipLaunchKernelGGL((k_gemm_tn<false, true>), dim3(gm, gn, S),
                            dim3(GEMM_THREADS), 0, stream.stream(), a, b,
                            nullptr, slab.data_ptr<float>(), M, N, K,
-                           k_per_split);
+                           k_per_split, drop);
         HIP_CHECK_LAST();
         long MN = (long)M * N;
         int blocks = std::min<long>(4096, ceil_div_i(MN, 256));
         if (out_f32)
             hipLaunchKernelGGL(k_splitk_combine<true>, dim3(blocks), dim3(256),
                                0, stream.stream(), slab.data_ptr<float>(), S,
-                               MN, N, bp, C.data_ptr());
-        else
+                               MN, N, bp, C.data_ptr(), drop);
+        else if (epi == EPI_NONE)
             hipLaunchKernelGGL(k_splitk_combine<false>, dim3(blocks), dim3(256),
                                0, stream.stream(), slab.data_ptr<float>(), S,
-                               MN, N, bp, C.data_ptr());
+                               MN, N, bp, C.data_ptr(), drop);
+        else {
+            // four elements per thread
+            blocks = std::min<long>(4096, ceil_div_i((MN + 3) / 4, 256));
+            if (epi == EPI_RELU)
+                hipLaunchKernelGGL((k_splitk_combine<false, EPI_RELU>),
+                                   dim3(blocks), dim3(256), 0, stream.stream(),
+                                   slab.data_ptr<float>(), S, MN, N, bp,
+                                   C.data_ptr(), drop);
+            else
+                hipLaunchKernelGGL((k_splitk_combine<false, EPI_RELU_DROP>),
+                                   dim3(blocks), dim3(256), 0, stream.stream(),
+                                   slab.data_ptr<float>(), S, MN, N, bp,
+                                   C.data_ptr(), drop);
+        }
         HIP_CHECK_LAST();
     } else {
         if (out_f32)
             hipLaunchKernelGGL((k_gemm_tn<true, false>), dim3(gm, gn, 1),
                                dim3(GEMM_THREADS), 0, stream.stream(), a, b,
-                               bp, C.data_ptr(), M, N, K, K);
-        else
+                               bp, C.data_ptr(), M, N, K, K, drop);
+        else if (epi == EPI_NONE)
             hipLaunchKernelGGL((k_gemm_tn<false, false>), dim3(gm, gn, 1),
                                dim3(GEMM_THREADS), 0, stream.stream(), a, b,
-                               bp, C.data_ptr(), M, N, K, K);
+                               bp, C.data_ptr(), M, N, K, K, drop);
+        else if (epi == EPI_RELU)
+            hipLaunchKernelGGL((k_gemm_tn<false, false, EPI_RELU>),
+                               dim3(gm, gn, 1), dim3(GEMM_THREADS), 0,
+                               stream.stream(), a, b, bp, C.data_ptr(), M, N,
+                               K, K, drop);
+        else
+            hipLaunchKernelGGL((k_gemm_tn<false, false, EPI_RELU_DROP>),
+                               dim3(gm, gn, 1), dim3(GEMM_THREADS), 0,
+                               stream.stream(), a, b, bp, C.data_ptr(), M, N,
+                               K, K, drop);
         HIP_CHECK_LAST();
     }
 }
@@ -463,6 +585,64 @@ at::Tensor linear_fwd(at::Tensor x, at::Tensor w,
     return gemm_tn(x, w, bias, /*out_f32=*/false);
 }
 
+// elementwise.hip
+at::Tensor relu_dropout_fwd(at::Tensor x, long thr, double scale,
+                            long call_seed);
+
+static void check_drop_args(long thr, double scale) {
+    TORCH_CHECK(thr >= 0 && thr <= 65535, "dropout threshold ", thr,
+                " outside [0, 65535]");
+    TORCH_CHECK(thr != 0 || scale == 1.0, "thr == 0 needs scale == 1");
+}
+
+at::Tensor linear_act_fwd(at::Tensor x, at::Tensor w,
+                          c10::optional<at::Tensor> bias, long thr,
+                          double scale, long call_seed) {
+    // y [M,N] bf16 = dropout(relu(x·w^T + bias)); thr == 0 is ReLU alone.
+    // call_seed carries the 64 seed bits (as int64).
+    check_drop_args(thr, scale);
+    TORCH_CHECK(x.is_cuda() && x.dim() == 2 &&
+                x.scalar_type() == at::kBFloat16 && x.is_contiguous());
+    TORCH_CHECK(w.is_cuda() && w.dim() == 2 &&
+                w.scalar_type() == at::kBFloat16 && w.is_contiguous());
+    TORCH_CHECK(x.size(1) == w.size(1), "K mismatch");
+    TORCH_CHECK(!bias.has_value() ||
+                (bias->is_cuda() && bias->scalar_type() == at::kFloat &&
+                 bias->is_contiguous() && bias->numel() == w.size(0)),
+                "bias: contiguous cuda fp32 [N]");
+    int M = x.size(0), N = w.size(0);
+    if (N <= 16)    // small-N kernel, then the elementwise epilogue
+        return relu_dropout_fwd(linear_fwd(x, w, bias), thr, scale, call_seed);
+    auto y = at::empty({M, N}, x.options());
+    DropArgs drop{(unsigned long long)call_seed, (unsigned)thr, (float)scale};
+    launch_gemm_tn(x, w, bias, y, /*out_f32=*/false,
+                   thr == 0 ? EPI_RELU : EPI_RELU_DROP, drop);
+    return y;
+}
+
+at::Tensor relu_drop_bwd(at::Tensor dy, at::Tensor y, double scale) {
+    TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == at::kBFloat16 &&
+                dy.is_contiguous() && y.is_cuda() &&
+                y.scalar_type() == at::kBFloat16 && y.is_contiguous() &&
+                dy.sizes() == y.sizes(),
+                "relu_drop_bwd: contiguous cuda bf16 dy and y of one shape");
+    auto dz = at::empty_like(dy);
+    long n = dy.numel();
+    if (n == 0) return dz;
+    int aligned = (((uintptr_t)dy.data_ptr() | (uintptr_t)y.data_ptr() |
+                    (uintptr_t)dz.data_ptr()) & 15) == 0;
+    int blocks = (int)std::min<long>(4096, ceil_div_i(ceil_div_i(n, 8), 256));
+    auto stream = at::hip::getCurrentHIPStream();
+    hipLaunchKernelGGL(k_relu_drop_bwd, dim3(blocks), dim3(256), 0,
+                       stream.stream(),
+                       reinterpret_cast<const bf16*>(dy.data_ptr()),
+                       reinterpret_cast<const bf16*>(y.data_ptr()),
+                       reinterpret_cast<bf16*>(dz.data_ptr()), n,
+                       (float)scale, aligned);
+    HIP_CHECK_LAST();
+    return dz;
+}
+
 at::Tensor linear_dgrad(at::Tensor dy, at::Tensor w) {
     // dy [M,N] bf16, w [N,K] -> dx [M,K] = dy·w
     int M = dy.size(0), N = dy.size(1), K = w.size(1);
@@ -505,7 +685,7 @@ at::Tensor linear_wgrad(at::Tensor dy, at::Tensor x) {
         int cblocks = std::min<long>(4096, ceil_div_i(MN, 256));
         hipLaunchKernelGGL(k_splitk_combine<true>, dim3(cblocks), dim3(256), 0,
                            stream.stream(), slab.data_ptr<float>(), S, MN, K,
-                           nullptr, dw.data_ptr());
+                           nullptr, dw.data_ptr(), DropArgs{0ull, 0u, 1.0f});
         HIP_CHECK_LAST();
         return dw;
     }

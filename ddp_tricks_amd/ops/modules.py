@@ -114,6 +114,23 @@ class ReLU(nn.ReLU):
         return F_ops.relu(x, inplace=self.inplace)
 
 
+class Dropout(nn.Dropout):
+    """``nn.Dropout`` on the counter-hash mask of ``ops.dropout_rng`` (same
+    mask on CPU and GPU, reproducible across a resume).  Stateless; in eval
+    mode, or with a ``p`` that rounds to 0, forward returns its input object
+    and launches nothing.  After a Linear + ReLU, route the junction through
+    ``linear_relu_dropout`` instead so the mask rides in the GEMM epilogue."""
+
+    def __init__(self, p: float = 0.5, inplace: bool = False):
+        if inplace:
+            raise ValueError("ops.modules.Dropout does not run in place")
+        super().__init__(p=p, inplace=False)
+        F_ops.dropout_threshold(p)      # range check
+
+    def forward(self, x):
+        return F_ops.dropout(x, self.p, self.training)
+
+
 class MaxPool2d(nn.MaxPool2d):
     def forward(self, x):
         return F_ops.max_pool2d(x, self.kernel_size, self.stride, self.padding)

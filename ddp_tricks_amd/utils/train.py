@@ -23,7 +23,8 @@ import torch
 from torch.utils.data import DataLoader
 
 from .. import amp
-from ..models import build_model
+from ..models import build_model, model_accepts
+from ..ops import dropout_rng
 from ..ops.optim import FusedLARS, FusedSGD, lars_param_groups
 from ..parallel.ddp import DistributedDataParallel as DDP
 from .callbacks import EarlyStopping, same_seeds
@@ -48,6 +49,29 @@ def _resolve_device(local_rank):
     return torch.device("cpu")
 
 
+def resolve_model_kwargs(args, model_name: str, dataset_name: str) -> dict:
+    """Constructor keywords of ``--model`` for this run: the caller's
+    ``args.model_kwargs``, the CIFAR head/stem defaults, and ``--dropout``
+    (only when > 0, so the default builds exactly the default model)."""
+    model_kwargs = dict(getattr(args, "model_kwargs", None) or {})
+    if model_name.startswith("resnet") and dataset_name == "cifar10":
+        model_kwargs.setdefault("num_classes", 10)
+        model_kwargs.setdefault("cifar_stem", True)
+    if model_name.startswith("vgg") and dataset_name == "cifar10":
+        model_kwargs.setdefault("num_classes", 10)
+        model_kwargs.setdefault("cifar_head", True)
+    dropout = float(getattr(args, "dropout", 0.0) or 0.0)
+    if dropout < 0.0:
+        raise ValueError("--dropout must be >= 0")
+    if dropout > 0:
+        if not model_accepts(model_name, "dropout"):
+            raise ValueError(f"--dropout: model {model_name!r} has no "
+                             "dropout layers (its constructor takes no "
+                             "'dropout' argument)")
+        model_kwargs["dropout"] = dropout
+    return model_kwargs
+
+
 def train(args):
     local_rank = getattr(args, "local_rank", 0) or 0
     device = _resolve_device(local_rank)
@@ -57,13 +81,10 @@ def train(args):
     # from the sidecar checkpoint.  Defaults reproduce the reference.
     model_name = getattr(args, "model", None) or "toy_net"
     dataset_name = getattr(args, "dataset", None) or "mnist"
-    model_kwargs = dict(getattr(args, "model_kwargs", None) or {})
-    if model_name.startswith("resnet") and dataset_name == "cifar10":
-        model_kwargs.setdefault("num_classes", 10)
-        model_kwargs.setdefault("cifar_stem", True)
-    if model_name.startswith("vgg") and dataset_name == "cifar10":
-        model_kwargs.setdefault("num_classes", 10)
-        model_kwargs.setdefault("cifar_head", True)
+    model_kwargs = resolve_model_kwargs(args, model_name, dataset_name)
+    # the dropout stream is keyed by (seed, rank); the process group (if
+    # any) is up by now
+    dropout_rng.seed(args.seed_num)
     Dataset = DATASETS[dataset_name]
 
     # Data pipeline (reference utils/train.py:24-30: sharded train loader,
@@ -241,6 +262,7 @@ def train(args):
     for epoch in range(start_epoch, args.epochs):
         epoch_start_time = time.time()
         train_sampler.set_epoch(epoch)
+        dropout_rng.set_epoch(epoch)   # restarts the per-epoch call counter
 
         parallel_model.train()
         train_loss, train_acc, curr_lr = iterate_loader(

@@ -82,6 +82,11 @@ def parse_args():
                              "adapted tensors only)")
     parser.add_argument("--lars_eta", default=0.001, type=float,
                         help="LARS trust coefficient")
+    parser.add_argument("--dropout", default=0.0, type=float,
+                        help="dropout probability of the model's dropout "
+                             "slots (vgg16's classifier); masks are a "
+                             "counter hash of (seed, rank, epoch, call), "
+                             "fused into the linear epilogue (0 = off)")
     args = parser.parse_args()
     if args.local_rank is None:
         args.local_rank = int(os.environ.get("LOCAL_RANK", 0))
