@@ -116,15 +116,16 @@ def _clip_buffers(device, nchunks: int = 0):
 
 
 def _clip_fused(optimizer) -> bool:
-    """Lazy clip only when the step that follows is the fused SGD or the
-    fused LARS (possibly under Lookahead) — they are the consumers of the
-    pending coefficient; any other optimizer gets its gradients clipped in
-    place."""
+    """Lazy clip only when the step that follows is the fused SGD, LARS,
+    AdamW or LAMB (possibly under Lookahead) — they are the consumers of
+    the pending coefficient; any other optimizer gets its gradients clipped
+    in place."""
     if os.environ.get("DDPX_CLIP_FUSED", "1") == "0":
         return False
-    from ..ops.optim import FusedLARS, FusedSGD
+    from ..ops.optim import FusedAdamW, FusedLAMB, FusedLARS, FusedSGD
+    fused = (FusedSGD, FusedLARS, FusedAdamW, FusedLAMB)
     inner = optimizer
-    while inner is not None and not isinstance(inner, (FusedSGD, FusedLARS)):
+    while inner is not None and not isinstance(inner, fused):
         inner = getattr(inner, "optimizer", None)
     return inner is not None
 

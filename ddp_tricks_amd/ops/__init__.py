@@ -116,3 +116,6 @@ from .functional import (  # noqa: E402,F401
 )
 from .modules import Dropout  # noqa: E402,F401
 from .optim import FusedSGD, FusedLARS, lars_param_groups  # noqa: E402,F401
+from .optim import (  # noqa: E402,F401
+    FusedAdamW, FusedLAMB, decay_param_groups,
+)

@@ -22,6 +22,22 @@ void fused_lars(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
                 double nesterov, double eta, double eps, bool trust_clip,
                 c10::optional<at::Tensor> found_inf,
                 c10::optional<at::Tensor> grad_scale);
+void fused_adamw(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
+                 std::vector<at::Tensor> exp_avgs,
+                 std::vector<at::Tensor> exp_avg_sqs, at::Tensor steps,
+                 at::Tensor coefs, double lr, double beta1, double beta2,
+                 double eps, double wd, bool decoupled,
+                 c10::optional<at::Tensor> found_inf,
+                 c10::optional<at::Tensor> grad_scale);
+void fused_lamb(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
+                std::vector<at::Tensor> exp_avgs,
+                std::vector<at::Tensor> exp_avg_sqs, at::Tensor steps,
+                at::Tensor coefs, at::Tensor partials, at::Tensor ratios,
+                double lr, double beta1, double beta2, double eps, double wd,
+                bool trust_clip, double max_trust,
+                c10::optional<at::Tensor> found_inf,
+                c10::optional<at::Tensor> grad_scale);
+long adam_ncoef();
 void fused_lookahead(std::vector<at::Tensor> fast, std::vector<at::Tensor> slow,
                      double alpha, c10::optional<at::Tensor> found_inf);
 at::Tensor cast_to_bf16(at::Tensor x);
@@ -192,6 +208,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("partials"), py::arg("ratios"), py::arg("lr"),
           py::arg("momentum"), py::arg("wd"), py::arg("nesterov"),
           py::arg("eta"), py::arg("eps"), py::arg("trust_clip"),
+          py::arg("found_inf") = c10::nullopt,
+          py::arg("grad_scale") = c10::nullopt);
+    m.attr("ADAM_NCOEF") = adam_ncoef();
+    m.def("fused_adamw", &fused_adamw,
+          "fused AdamW step with a device-side step counter: steps holds one "
+          "float per tensor, coefs ADAM_NCOEF per tensor (list order); both "
+          "stay untouched when found_inf is set",
+          py::arg("params"), py::arg("grads"), py::arg("exp_avgs"),
+          py::arg("exp_avg_sqs"), py::arg("steps"), py::arg("coefs"),
+          py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
+          py::arg("wd"), py::arg("decoupled"),
+          py::arg("found_inf") = c10::nullopt,
+          py::arg("grad_scale") = c10::nullopt);
+    m.def("fused_lamb", &fused_lamb,
+          "fused LAMB step: the AdamW counter and moments, per-tensor trust "
+          "ratios |p|/|u| (two partials per chunk, one ratio per tensor)",
+          py::arg("params"), py::arg("grads"), py::arg("exp_avgs"),
+          py::arg("exp_avg_sqs"), py::arg("steps"), py::arg("coefs"),
+          py::arg("partials"), py::arg("ratios"), py::arg("lr"),
+          py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("wd"),
+          py::arg("trust_clip"), py::arg("max_trust"),
           py::arg("found_inf") = c10::nullopt,
           py::arg("grad_scale") = c10::nullopt);
     m.def("fused_lookahead", &fused_lookahead, "fused Lookahead interpolation",

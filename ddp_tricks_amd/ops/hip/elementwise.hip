@@ -9,6 +9,8 @@
 // device), and the coefficient applied inside the SGD's gradient read.
 // Fused LARS adds per-tensor reductions on the same (tensor, chunk) scheme:
 // pair square sums, a per-tensor trust ratio, and the SGD body with it.
+// Fused AdamW and LAMB add a device-side step counter (k_mt_adam_tick), so
+// that an overflow-skipped step does not advance the bias correction.
 //
 // Multi-tensor scheme: host packs up to MT_MAX tensor pointers + a prefix
 // of chunk offsets into the kernarg struct; blocks map to (tensor, chunk)
@@ -680,6 +682,484 @@ void fused_lars(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
         chunk_base += chunks;
     }
 }
+
+// ------------------------------------------------------ fused AdamW / LAMB ---
+
+// Adam needs four arrays per tensor, one more than MTMeta holds.  A sibling
+// struct (MTMeta and its kernels stay as they are); same (tensor, chunk)
+// mapping, same MT_MAX / MT_CHUNK, global tensor and chunk indices.
+struct MTMeta4 {
+    const float* __restrict__ g[MT_MAX];
+    float* __restrict__ p[MT_MAX];
+    float* __restrict__ m[MT_MAX];
+    float* __restrict__ v[MT_MAX];
+    long sizes[MT_MAX];
+    int chunk_start[MT_MAX + 1];
+    int ntensors;
+};
+
+DEV_INLINE void chunk_range(const MTMeta4& m, int& t, long& base, long& end) {
+    const int chunk = blockIdx.x;
+    t = 0;
+    while (t + 1 < m.ntensors && m.chunk_start[t + 1] <= chunk) ++t;
+    long n = m.sizes[t];
+    base = (long)(chunk - m.chunk_start[t]) * MT_CHUNK;
+    end = base + MT_CHUNK < n ? base + MT_CHUNK : n;
+}
+
+// Per-tensor bias-correction coefficients of the current step, written by
+// the tick and read by the step kernels: ADAM_NCOEF floats per tensor,
+//   [0] lr / bc1      [1] sqrt(bc2)      [2] bc1      [3] bc2
+// bc1 = 1 - beta1^step, bc2 = 1 - beta2^step.
+constexpr int ADAM_NCOEF = 4;
+
+// The step counter.  One thread per tensor of the launch group:
+// steps[t] += 1 (fp32, exact below 2^24) and the coefficients of the new
+// step, each computed in double and rounded to fp32 once.  It returns at
+// once when found_inf is set, so a step that the amp overflow flag skips
+// does not advance the bias correction.
+__global__ void k_mt_adam_tick(float* __restrict__ steps,
+                               float* __restrict__ coefs, int tensor_base,
+                               int ntensors, double lr, double beta1,
+                               double beta2,
+                               const float* __restrict__ found_inf) {
+    if (found_inf && *found_inf != 0.0f) return;
+    const int t = threadIdx.x;
+    if (t >= ntensors) return;
+    const long k = (long)tensor_base + t;
+    const float s = steps[k] + 1.0f;
+    steps[k] = s;
+    const double bc1 = 1.0 - pow(beta1, (double)s);
+    const double bc2 = 1.0 - pow(beta2, (double)s);
+    coefs[ADAM_NCOEF * k + 0] = (float)(lr / bc1);
+    coefs[ADAM_NCOEF * k + 1] = (float)sqrt(bc2);
+    coefs[ADAM_NCOEF * k + 2] = (float)bc1;
+    coefs[ADAM_NCOEF * k + 3] = (float)bc2;
+}
+
+// Host-rounded constants of one step (each a double rounded to fp32 once).
+struct AdamK {
+    float b1, omb1;   // beta1, 1 - beta1
+    float b2, omb2;   // beta2, 1 - beta2
+    float eps;
+    float wd;         // coupled (plain Adam) decay, and LAMB's wd
+    float decay;      // 1 - lr*wd, the decoupled decay factor
+    int decoupled;
+};
+
+// Moment update shared by AdamW and LAMB, one rounding per line:
+//   t1 = omb1 * g            m = fma(b1, m, t1)
+//   t2 = omb2 * g            t3 = t2 * g            v = fma(b2, v, t3)
+DEV_INLINE void adam_moments(float g, float& m, float& v, const AdamK& k) {
+    #pragma clang fp contract(off)
+    m = fmaf(k.b1, m, __fmul_rn(k.omb1, g));
+    v = fmaf(k.b2, v, __fmul_rn(__fmul_rn(k.omb2, g), g));
+}
+
+// The AdamW element update, exact fp32 operation order (one rounding each):
+//   g  = g * gs                          (GS only)
+//   g  = fma(wd, p, g)                   (plain Adam: !decoupled, wd != 0)
+//   m, v                                 adam_moments
+//   p  = p * decay                       (decoupled, wd != 0)
+//   s  = sqrt(v)            q = s / c1         d = q + eps
+//   r  = m / d              p = fma(-c0, r, p)
+// c0 = lr/bc1, c1 = sqrt(bc2) from the tick.  sqrt and / are the correctly
+// rounded ones (no fast-math in this build).
+template <bool GS>
+DEV_INLINE void adamw_elem(float g, float& p, float& m, float& v, float gs,
+                           const AdamK& k, float c0, float c1) {
+    #pragma clang fp contract(off)
+    if (GS) g = __fmul_rn(g, gs);
+    if (!k.decoupled && k.wd != 0.0f) g = fmaf(k.wd, p, g);
+    adam_moments(g, m, v, k);
+    if (k.decoupled && k.wd != 0.0f) p = __fmul_rn(p, k.decay);
+    const float d = __fadd_rn(__fdiv_rn(sqrtf(v), c1), k.eps);
+    p = fmaf(-c0, __fdiv_rn(m, d), p);
+}
+
+// One pass per (tensor, chunk): reads g, p, m, v, writes p, m, v; f32x4
+// body and scalar tail as k_mt_sgd.  Device-side no-op under found_inf.
+// GS reads the gradient as __fmul_rn(g, *grad_scale): bitwise k_mt_scale
+// followed by the GS=false kernel.
+template <bool GS>
+__global__ void k_mt_adamw(MTMeta4 mt, AdamK k,
+                           const float* __restrict__ coefs, int tensor_base,
+                           const float* __restrict__ found_inf,
+                           const float* __restrict__ grad_scale) {
+    if (found_inf && *found_inf != 0.0f) return;
+    const float gs = GS ? *grad_scale : 1.0f;
+    int t; long base, end;
+    chunk_range(mt, t, base, end);
+    const float* __restrict__ cf = coefs + ADAM_NCOEF * ((long)tensor_base + t);
+    const float c0 = cf[0], c1 = cf[1];
+    const float* __restrict__ g = mt.g[t];
+    float* __restrict__ p = mt.p[t];
+    float* __restrict__ m = mt.m[t];
+    float* __restrict__ v = mt.v[t];
+    long vb = base >> 2, ve = end >> 2;
+    for (long i = vb + threadIdx.x; i < ve; i += MT_BLOCK) {
+        f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+        f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
+        f32x4 mv = reinterpret_cast<f32x4*>(m)[i];
+        f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
+        #pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float pj = pv[j], mj = mv[j], vj = vv[j];
+            adamw_elem<GS>(gv[j], pj, mj, vj, gs, k, c0, c1);
+            pv[j] = pj; mv[j] = mj; vv[j] = vj;
+        }
+        reinterpret_cast<f32x4*>(p)[i] = pv;
+        reinterpret_cast<f32x4*>(m)[i] = mv;
+        reinterpret_cast<f32x4*>(v)[i] = vv;
+    }
+    for (long i = ve * 4 + threadIdx.x; i < end; i += MT_BLOCK) {
+        float pj = p[i], mj = m[i], vj = v[i];
+        adamw_elem<GS>(g[i], pj, mj, vj, gs, k, c0, c1);
+        p[i] = pj; m[i] = mj; v[i] = vj;
+    }
+}
+
+// LAMB's update direction from the stored moments and the parameter, one
+// rounding each:
+//   mh = m / bc1      vh = v / bc2      s = sqrt(vh)      d = s + eps
+//   q  = mh / d       u  = fma(wd, p, q)   (wd != 0; else u = q)
+// Both the moments kernel (for |u|) and the step kernel call it on the same
+// m, v, p, so no update buffer is needed.
+DEV_INLINE float lamb_u(float p, float m, float v, float bc1, float bc2,
+                        float eps, float wd) {
+    #pragma clang fp contract(off)
+    const float mh = __fdiv_rn(m, bc1);
+    const float d = __fadd_rn(sqrtf(__fdiv_rn(v, bc2)), eps);
+    const float q = __fdiv_rn(mh, d);
+    return wd != 0.0f ? fmaf(wd, p, q) : q;
+}
+
+// LAMB launch 1: m and v in place (adam_moments on g*gs), then per-chunk
+// sums of p^2 and u^2 in k_mt_lars_sqsum's layout: partials[2*c] = sum p^2,
+// partials[2*c+1] = sum u^2, c the global chunk.  p is not written.
+template <bool GS>
+__global__ void k_mt_lamb_moments(MTMeta4 mt, AdamK k,
+                                  const float* __restrict__ coefs,
+                                  int tensor_base,
+                                  const float* __restrict__ found_inf,
+                                  const float* __restrict__ grad_scale,
+                                  float* __restrict__ partials,
+                                  int chunk_base) {
+    if (found_inf && *found_inf != 0.0f) return;
+    const float gs = GS ? *grad_scale : 1.0f;
+    int t; long base, end;
+    chunk_range(mt, t, base, end);
+    const float* __restrict__ cf = coefs + ADAM_NCOEF * ((long)tensor_base + t);
+    const float bc1 = cf[2], bc2 = cf[3];
+    const float* __restrict__ g = mt.g[t];
+    const float* __restrict__ p = mt.p[t];
+    float* __restrict__ m = mt.m[t];
+    float* __restrict__ v = mt.v[t];
+    float accp = 0.f, accu = 0.f;
+    long vb = base >> 2, ve = end >> 2;
+    for (long i = vb + threadIdx.x; i < ve; i += MT_BLOCK) {
+        f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+        f32x4 pv = reinterpret_cast<const f32x4*>(p)[i];
+        f32x4 mv = reinterpret_cast<f32x4*>(m)[i];
+        f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
+        #pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float gj = gv[j], mj = mv[j], vj = vv[j];
+            if (GS) gj = __fmul_rn(gj, gs);
+            adam_moments(gj, mj, vj, k);
+            mv[j] = mj; vv[j] = vj;
+            const float u = lamb_u(pv[j], mj, vj, bc1, bc2, k.eps, k.wd);
+            accp = fmaf(pv[j], pv[j], accp);
+            accu = fmaf(u, u, accu);
+        }
+        reinterpret_cast<f32x4*>(m)[i] = mv;
+        reinterpret_cast<f32x4*>(v)[i] = vv;
+    }
+    for (long i = ve * 4 + threadIdx.x; i < end; i += MT_BLOCK) {
+        float gj = g[i], mj = m[i], vj = v[i];
+        if (GS) gj = __fmul_rn(gj, gs);
+        adam_moments(gj, mj, vj, k);
+        m[i] = mj; v[i] = vj;
+        const float u = lamb_u(p[i], mj, vj, bc1, bc2, k.eps, k.wd);
+        accp = fmaf(p[i], p[i], accp);
+        accu = fmaf(u, u, accu);
+    }
+    float sp = mt_block_sum(accp);
+    __syncthreads();  // mt_block_sum's LDS is reused by the second sum
+    float su = mt_block_sum(accu);
+    if (threadIdx.x == 0) {
+        long c = (long)chunk_base + blockIdx.x;
+        partials[2 * c] = sp;
+        partials[2 * c + 1] = su;
+    }
+}
+
+// LAMB launch 2: one block per tensor, the summation scheme of
+// k_mt_lars_ratio.  r = |p| / |u| if both > 0 else 1, min(r, max_trust) with
+// trust_clip; formed in double, rounded once.
+__global__ void k_mt_lamb_ratio(MTMeta4 mt, const float* __restrict__ partials,
+                                int chunk_base, float* __restrict__ ratios,
+                                int tensor_base, int trust_clip,
+                                double max_trust,
+                                const float* __restrict__ found_inf) {
+    if (found_inf && *found_inf != 0.0f) return;
+    __shared__ double redp[MT_BLOCK];
+    __shared__ double redu[MT_BLOCK];
+    const int t = blockIdx.x;
+    const int c0 = mt.chunk_start[t], c1 = mt.chunk_start[t + 1];
+    double sp = 0.0, su = 0.0;
+    for (int c = c0 + threadIdx.x; c < c1; c += MT_BLOCK) {
+        long k = 2 * ((long)chunk_base + c);
+        sp += (double)partials[k];
+        su += (double)partials[k + 1];
+    }
+    redp[threadIdx.x] = sp;
+    redu[threadIdx.x] = su;
+    __syncthreads();
+    #pragma unroll
+    for (int w = MT_BLOCK / 2; w > 0; w >>= 1) {
+        if (threadIdx.x < w) {
+            redp[threadIdx.x] += redp[threadIdx.x + w];
+            redu[threadIdx.x] += redu[threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const double wn = sqrt(redp[0]), un = sqrt(redu[0]);
+    double r = 1.0;
+    if (wn > 0.0 && un > 0.0) {
+        r = wn / un;
+        if (trust_clip) r = fmin(r, max_trust);
+    }
+    ratios[tensor_base + t] = (float)r;
+}
+
+// LAMB launch 3: u again from the stored m, v and the still-unchanged p
+// (lamb_u, the same bits as launch 1 saw), then
+//   a = lr * r (one rounding)      p = fma(-a, u, p)
+__global__ void k_mt_lamb_step(MTMeta4 mt, float lr, float eps, float wd,
+                               const float* __restrict__ coefs,
+                               const float* __restrict__ ratios,
+                               int tensor_base,
+                               const float* __restrict__ found_inf) {
+    if (found_inf && *found_inf != 0.0f) return;
+    int t; long base, end;
+    chunk_range(mt, t, base, end);
+    const float* __restrict__ cf = coefs + ADAM_NCOEF * ((long)tensor_base + t);
+    const float bc1 = cf[2], bc2 = cf[3];
+    const float a = __fmul_rn(lr, ratios[tensor_base + t]);
+    float* __restrict__ p = mt.p[t];
+    const float* __restrict__ m = mt.m[t];
+    const float* __restrict__ v = mt.v[t];
+    long vb = base >> 2, ve = end >> 2;
+    for (long i = vb + threadIdx.x; i < ve; i += MT_BLOCK) {
+        f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
+        f32x4 mv = reinterpret_cast<const f32x4*>(m)[i];
+        f32x4 vv = reinterpret_cast<const f32x4*>(v)[i];
+        #pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float u = lamb_u(pv[j], mv[j], vv[j], bc1, bc2, eps, wd);
+            pv[j] = fmaf(-a, u, pv[j]);
+        }
+        reinterpret_cast<f32x4*>(p)[i] = pv;
+    }
+    for (long i = ve * 4 + threadIdx.x; i < end; i += MT_BLOCK) {
+        const float u = lamb_u(p[i], m[i], v[i], bc1, bc2, eps, wd);
+        p[i] = fmaf(-a, u, p[i]);
+    }
+}
+
+// Operand checks shared by fused_adamw and fused_lamb.  steps: one float
+// per tensor, coefs: ADAM_NCOEF per tensor, both in list order.
+static void adam_check(const char* who, const std::vector<at::Tensor>& params,
+                       const std::vector<at::Tensor>& grads,
+                       const std::vector<at::Tensor>& exp_avgs,
+                       const std::vector<at::Tensor>& exp_avg_sqs,
+                       const at::Tensor& steps, const at::Tensor& coefs,
+                       const c10::optional<at::Tensor>& found_inf,
+                       const c10::optional<at::Tensor>& grad_scale) {
+    const size_t n = params.size();
+    TORCH_CHECK(grads.size() == n && exp_avgs.size() == n &&
+                exp_avg_sqs.size() == n, who, ": list lengths differ");
+    TORCH_CHECK(n < (1UL << 28), who, ": list too long");
+    auto ok = [](const at::Tensor& x, long numel) {
+        return x.is_cuda() && x.scalar_type() == at::kFloat &&
+               x.is_contiguous() && x.numel() == numel;
+    };
+    for (size_t i = 0; i < n; ++i) {
+        const long ne = params[i].numel();
+        TORCH_CHECK(ok(params[i], ne) && ok(grads[i], ne), who,
+                    " expects contiguous cuda fp32 params and same-size "
+                    "grads");
+        TORCH_CHECK(ok(exp_avgs[i], ne) && ok(exp_avg_sqs[i], ne), who,
+                    ": exp_avg / exp_avg_sq must match their parameter");
+    }
+    TORCH_CHECK(steps.is_cuda() && steps.scalar_type() == at::kFloat &&
+                steps.is_contiguous() && steps.numel() >= (long)n,
+                who, ": steps holds ", steps.numel(), " floats, need ", n,
+                " (one per tensor)");
+    TORCH_CHECK(coefs.is_cuda() && coefs.scalar_type() == at::kFloat &&
+                coefs.is_contiguous() &&
+                coefs.numel() >= (long)(ADAM_NCOEF * n),
+                who, ": coefs holds ", coefs.numel(), " floats, need ",
+                ADAM_NCOEF * n, " (", ADAM_NCOEF, " per tensor)");
+    TORCH_CHECK(!found_inf.has_value() ||
+                (found_inf->is_cuda() &&
+                 found_inf->scalar_type() == at::kFloat &&
+                 found_inf->numel() >= 1),
+                who, ": found_inf must be a cuda fp32 tensor");
+    TORCH_CHECK(!grad_scale.has_value() ||
+                (grad_scale->is_cuda() &&
+                 grad_scale->scalar_type() == at::kFloat &&
+                 grad_scale->numel() >= 1),
+                who, ": grad_scale must be a cuda fp32 tensor");
+}
+
+// Fills the kernarg struct for tensors [start, start + MT_MAX); returns the
+// group's chunk count.
+static int adam_pack(MTMeta4& m, size_t start,
+                     const std::vector<at::Tensor>& params,
+                     const std::vector<at::Tensor>& grads,
+                     const std::vector<at::Tensor>& exp_avgs,
+                     const std::vector<at::Tensor>& exp_avg_sqs) {
+    int chunks = 0, nt = 0;
+    for (size_t i = start; i < std::min(params.size(), start + MT_MAX); ++i) {
+        m.g[nt] = grads[i].data_ptr<float>();
+        m.p[nt] = params[i].data_ptr<float>();
+        m.m[nt] = exp_avgs[i].data_ptr<float>();
+        m.v[nt] = exp_avg_sqs[i].data_ptr<float>();
+        m.sizes[nt] = params[i].numel();
+        m.chunk_start[nt] = chunks;
+        chunks += ceil_div_i(params[i].numel(), MT_CHUNK);
+        ++nt;
+    }
+    m.chunk_start[nt] = chunks;
+    m.ntensors = nt;
+    return chunks;
+}
+
+static AdamK adam_consts(double lr, double beta1, double beta2, double eps,
+                         double wd, bool decoupled) {
+    AdamK k;
+    k.b1 = (float)beta1;
+    k.omb1 = (float)(1.0 - beta1);
+    k.b2 = (float)beta2;
+    k.omb2 = (float)(1.0 - beta2);
+    k.eps = (float)eps;
+    k.wd = (float)wd;
+    k.decay = (float)(1.0 - lr * wd);
+    k.decoupled = decoupled ? 1 : 0;
+    return k;
+}
+
+// Tick + step per MT_MAX group.  No host sync, no H2D copy: everything the
+// kernels need travels in the kernarg or is already on the device.
+void fused_adamw(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
+                 std::vector<at::Tensor> exp_avgs,
+                 std::vector<at::Tensor> exp_avg_sqs, at::Tensor steps,
+                 at::Tensor coefs, double lr, double beta1, double beta2,
+                 double eps, double wd, bool decoupled,
+                 c10::optional<at::Tensor> found_inf,
+                 c10::optional<at::Tensor> grad_scale) {
+    adam_check("fused_adamw", params, grads, exp_avgs, exp_avg_sqs, steps,
+               coefs, found_inf, grad_scale);
+    mt_total_chunks(params);
+    auto stream = at::hip::getCurrentHIPStream();
+    const float* fi = found_inf.has_value()
+        ? found_inf->data_ptr<float>() : nullptr;
+    const float* gs = grad_scale.has_value()
+        ? grad_scale->data_ptr<float>() : nullptr;
+    float* sp = steps.data_ptr<float>();
+    float* cp = coefs.data_ptr<float>();
+    const AdamK k = adam_consts(lr, beta1, beta2, eps, wd, decoupled);
+    for (size_t start = 0; start < params.size(); start += MT_MAX) {
+        MTMeta4 m{};
+        int chunks = adam_pack(m, start, params, grads, exp_avgs, exp_avg_sqs);
+        hipLaunchKernelGGL(k_mt_adam_tick, dim3(1), dim3(MT_MAX), 0,
+                           stream.stream(), sp, cp, (int)start, m.ntensors,
+                           lr, beta1, beta2, fi);
+        HIP_CHECK_LAST();
+        if (chunks == 0) continue;
+        if (gs)
+            hipLaunchKernelGGL(k_mt_adamw<true>, dim3(chunks), dim3(MT_BLOCK),
+                               0, stream.stream(), m, k, cp, (int)start, fi,
+                               gs);
+        else
+            hipLaunchKernelGGL(k_mt_adamw<false>, dim3(chunks),
+                               dim3(MT_BLOCK), 0, stream.stream(), m, k, cp,
+                               (int)start, fi, gs);
+        HIP_CHECK_LAST();
+    }
+}
+
+// Tick + moments + ratio + step per MT_MAX group.  partials: 2 floats per
+// (tensor, chunk); ratios: one float per tensor, list order; both indexed
+// globally over the whole list.
+void fused_lamb(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
+                std::vector<at::Tensor> exp_avgs,
+                std::vector<at::Tensor> exp_avg_sqs, at::Tensor steps,
+                at::Tensor coefs, at::Tensor partials, at::Tensor ratios,
+                double lr, double beta1, double beta2, double eps, double wd,
+                bool trust_clip, double max_trust,
+                c10::optional<at::Tensor> found_inf,
+                c10::optional<at::Tensor> grad_scale) {
+    adam_check("fused_lamb", params, grads, exp_avgs, exp_avg_sqs, steps,
+               coefs, found_inf, grad_scale);
+    long total = mt_total_chunks(params);
+    TORCH_CHECK(2 * total < (1L << 31), "multi-tensor list too large");
+    TORCH_CHECK(partials.is_cuda() && partials.scalar_type() == at::kFloat &&
+                partials.is_contiguous() && partials.numel() >= 2 * total,
+                "fused_lamb: partials holds ", partials.numel(),
+                " floats, need ", 2 * total, " (two per chunk)");
+    TORCH_CHECK(ratios.is_cuda() && ratios.scalar_type() == at::kFloat &&
+                ratios.is_contiguous() &&
+                ratios.numel() >= (long)params.size(),
+                "fused_lamb: ratios holds ", ratios.numel(),
+                " floats, need ", params.size(), " (one per tensor)");
+    auto stream = at::hip::getCurrentHIPStream();
+    const float* fi = found_inf.has_value()
+        ? found_inf->data_ptr<float>() : nullptr;
+    const float* gs = grad_scale.has_value()
+        ? grad_scale->data_ptr<float>() : nullptr;
+    float* sp = steps.data_ptr<float>();
+    float* cp = coefs.data_ptr<float>();
+    float* pp = partials.data_ptr<float>();
+    float* rp = ratios.data_ptr<float>();
+    const AdamK k = adam_consts(lr, beta1, beta2, eps, wd, true);
+    int chunk_base = 0;
+    for (size_t start = 0; start < params.size(); start += MT_MAX) {
+        MTMeta4 m{};
+        int chunks = adam_pack(m, start, params, grads, exp_avgs, exp_avg_sqs);
+        hipLaunchKernelGGL(k_mt_adam_tick, dim3(1), dim3(MT_MAX), 0,
+                           stream.stream(), sp, cp, (int)start, m.ntensors,
+                           lr, beta1, beta2, fi);
+        HIP_CHECK_LAST();
+        if (chunks > 0) {
+            if (gs)
+                hipLaunchKernelGGL(k_mt_lamb_moments<true>, dim3(chunks),
+                                   dim3(MT_BLOCK), 0, stream.stream(), m, k,
+                                   cp, (int)start, fi, gs, pp, chunk_base);
+            else
+                hipLaunchKernelGGL(k_mt_lamb_moments<false>, dim3(chunks),
+                                   dim3(MT_BLOCK), 0, stream.stream(), m, k,
+                                   cp, (int)start, fi, gs, pp, chunk_base);
+            HIP_CHECK_LAST();
+        }
+        // also for a group of empty tensors: their ratios read 1
+        hipLaunchKernelGGL(k_mt_lamb_ratio, dim3(m.ntensors), dim3(MT_BLOCK),
+                           0, stream.stream(), m, pp, chunk_base, rp,
+                           (int)start, trust_clip ? 1 : 0, max_trust, fi);
+        HIP_CHECK_LAST();
+        if (chunks == 0) continue;
+        hipLaunchKernelGGL(k_mt_lamb_step, dim3(chunks), dim3(MT_BLOCK), 0,
+                           stream.stream(), m, (float)lr, k.eps, k.wd, cp, rp,
+                           (int)start, fi);
+        HIP_CHECK_LAST();
+        chunk_base += chunks;
+    }
+}
+
+long adam_ncoef() { return ADAM_NCOEF; }
 
 // --------------------------------------------------------------- lookahead ---
 

@@ -25,7 +25,8 @@ from torch.utils.data import DataLoader
 from .. import amp
 from ..models import build_model, model_accepts
 from ..ops import dropout_rng
-from ..ops.optim import FusedLARS, FusedSGD, lars_param_groups
+from ..ops.optim import (FusedAdamW, FusedLAMB, FusedLARS, FusedSGD,
+                         decay_param_groups, lars_param_groups)
 from ..parallel.ddp import DistributedDataParallel as DDP
 from .callbacks import EarlyStopping, same_seeds
 from .data import (DATASETS, Augment, CudaPrefetcher, DeviceBatchLoader,
@@ -176,8 +177,8 @@ def train(args):
 
     os.makedirs(os.path.join(args.model_path, "logs"), exist_ok=True)
     latest_model_path = os.path.join(args.model_path, args.exp_name)
-    # --optimizer / --weight_decay / --lars_eta (extension); the defaults
-    # build the reference's SGD(lr, momentum=0.9, nesterov=True)
+    # --optimizer / --weight_decay / --lars_eta / --adam_* (extension); the
+    # defaults build the reference's SGD(lr, momentum=0.9, nesterov=True)
     optimizer_name = getattr(args, "optimizer", None) or "sgd"
     weight_decay = float(getattr(args, "weight_decay", 0.0) or 0.0)
     if weight_decay < 0.0:
@@ -193,6 +194,19 @@ def train(args):
         optimizer = FusedLARS(lars_param_groups(model, weight_decay),
                               lr=args.learning_rate, momentum=0.9,
                               nesterov=True, trust_coefficient=lars_eta)
+    elif optimizer_name in ("adamw", "lamb"):
+        # Adam-class steps: --weight_decay is decoupled and skips BN
+        # scale/shift and biases (for lamb they also take the plain AdamW
+        # step); -l must be an Adam-scale rate
+        def flag(name, default):
+            value = getattr(args, name, None)
+            return default if value is None else float(value)
+        betas = (flag("adam_beta1", 0.9), flag("adam_beta2", 0.999))
+        adam_eps = flag("adam_eps", 1e-8)
+        cls = FusedAdamW if optimizer_name == "adamw" else FusedLAMB
+        optimizer = cls(decay_param_groups(model, weight_decay),
+                        lr=args.learning_rate, betas=betas, eps=adam_eps,
+                        weight_decay=weight_decay)
     else:
         raise ValueError(f"unknown optimizer {optimizer_name!r}")
     lookahead = Lookahead(optimizer=optimizer, k=10, alpha=0.5)

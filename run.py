@@ -73,13 +73,23 @@ def parse_args():
                              "loader (alpha = 1 boxes); implies "
                              "--device_data on GPU")
     parser.add_argument("--optimizer", default="sgd", type=str,
-                        choices=("sgd", "lars"),
+                        choices=("sgd", "lars", "adamw", "lamb"),
                         help="sgd: fused nesterov SGD; lars: the same step "
                              "with layer-wise trust ratios on the weights "
-                             "(BN parameters and biases are not adapted)")
+                             "(BN parameters and biases are not adapted); "
+                             "adamw: fused AdamW; lamb: Adam's direction "
+                             "with layer-wise trust ratios (pass an "
+                             "Adam-scale -l with these two)")
     parser.add_argument("--weight_decay", default=0.0, type=float,
                         help="L2 weight decay (with --optimizer lars: on the "
-                             "adapted tensors only)")
+                             "adapted tensors only; with adamw / lamb: "
+                             "decoupled, not on BN parameters and biases)")
+    parser.add_argument("--adam_beta1", default=0.9, type=float,
+                        help="adamw / lamb: first-moment decay")
+    parser.add_argument("--adam_beta2", default=0.999, type=float,
+                        help="adamw / lamb: second-moment decay")
+    parser.add_argument("--adam_eps", default=1e-8, type=float,
+                        help="adamw / lamb: epsilon of the denominator")
     parser.add_argument("--lars_eta", default=0.001, type=float,
                         help="LARS trust coefficient")
     parser.add_argument("--dropout", default=0.0, type=float,
