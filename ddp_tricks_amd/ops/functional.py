@@ -161,6 +161,37 @@ def _use_pad8(C: int, H: int, W: int) -> bool:
     return C < 8 and H * W >= 1024
 
 
+# ``stem`` argument of the C < 8 forward (ext.conv2d_stem_plan): -1 automatic,
+# 0 the MFMA path on padded channels, 1 forces the direct kernel
+STEM = -1
+
+
+def _stem_direct(ext, x, weight, stride, padding) -> bool:
+    """True when this forward runs the direct stem kernel, which reads the
+    unpadded bf16 x and the fp32 master weight (no padded copy, no packed
+    weight image)."""
+    K, C, R, S = weight.shape
+    if C >= 8 or weight.dtype != torch.float32:
+        return False
+    return ext.conv2d_stem_plan(x.shape[0], C, x.shape[2], x.shape[3], K,
+                                R, S, stride, padding, STEM) == "direct"
+
+
+def _stem_fwd(ctx, ext, x, weight, bias, stride, padding, want_stats):
+    """Direct stem forward; saves what _conv_bwd_impl expects (the padded
+    x only where the wgrad wants it)."""
+    xb = _chlast(_to_bf16(x))
+    pad8_bwd = _use_pad8(weight.shape[1], xb.shape[2], xb.shape[3])
+    y, stats = ext.conv2d_stem_fwd(
+        xb, weight.detach().contiguous(),
+        bias if bias is None else bias.detach().float(), stride, padding,
+        want_stats, STEM)
+    ctx.save_for_backward(_pad8(xb) if pad8_bwd else xb, weight)
+    ctx.meta = (stride, padding, x.dtype, weight.shape, bias is not None,
+                pad8_bwd)
+    return y, stats
+
+
 def _conv_fwd_prep(ctx, x, weight, bias, stride, padding):
     """Shared operand prep for the conv autograd functions; returns
     (ext, xb_for_kernel, wb, bias_f) and fills ctx bookkeeping."""
@@ -250,6 +281,12 @@ class _HIPConv2dStats(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, stride, padding):
+        ext = require_ext_for(x)
+        if _stem_direct(ext, x, weight, stride, padding):
+            y, stats = _stem_fwd(ctx, ext, x, weight, bias, stride, padding,
+                                 True)
+            ctx.mark_non_differentiable(stats)
+            return y, stats
         ext, xk, wb, bias_f = _conv_fwd_prep(ctx, x, weight, bias, stride,
                                              padding)
         y, stats = ext.conv2d_fwd_stats(xk, wb, bias_f, stride, padding)
@@ -266,15 +303,19 @@ class _HIPConv2d(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, stride, padding):
         ext = require_ext_for(x)
+        if _stem_direct(ext, x, weight, stride, padding):
+            return _stem_fwd(ctx, ext, x, weight, bias, stride, padding,
+                             False)[0]
         xb = _chlast(_to_bf16(x))
         C_in = weight.shape[1]
         if C_in < 8:
-            # fwd always takes the MFMA path on zero-padded channels
-            # (measured faster than the direct VALU kernel even at MNIST
-            # size: 48 vs 64 us).  wgrad for SMALL spatial inputs stays on
-            # the specialized C<8 kernels (measured: MFMA wgrad at Kgemm=72
-            # is 362 us vs 132 us for the sliding-window kernel), so the
-            # UNPADDED x is saved in that case.
+            # what the stem plan leaves (C = 3, strides, wide Ko) takes the
+            # MFMA path on zero-padded channels; the direct kernel serves
+            # the C = 1 3x3 stem (docs/KERNELS.md, "Direct stem forward").
+            # wgrad for SMALL spatial inputs stays on the specialized C<8
+            # kernels (measured: MFMA wgrad at Kgemm=72 is 362 us vs 132 us
+            # for the sliding-window kernel), so the UNPADDED x is saved in
+            # that case.
             pad8_bwd = _use_pad8(C_in, xb.shape[2], xb.shape[3])
             xp = _pad8(xb)
             wb = weight_variant(weight, "nhwc_p8")

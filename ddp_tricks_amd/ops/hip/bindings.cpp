@@ -143,6 +143,11 @@ at::Tensor conv2d_dgrad(at::Tensor dy, at::Tensor wt2, long N, long C, long H,
                         long W, long R, long S, long stride, long pad,
                         c10::optional<at::Tensor> addend, long group,
                         long kwalk);
+std::tuple<at::Tensor, at::Tensor> conv2d_stem_fwd(
+    at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias, long stride,
+    long pad, bool want_stats, long stem);
+std::string conv2d_stem_plan(long N, long C, long H, long W, long Ko, long R,
+                             long S, long stride, long pad, long stem);
 std::string conv2d_kloop_plan(long mode, long N, long C, long H, long W,
                               long Ko, long R, long S, long stride, long pad,
                               long kwalk);
@@ -347,6 +352,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("stride"), py::arg("pad"),
           py::arg("addend") = c10::nullopt, py::arg("group") = -1,
           py::arg("kwalk") = -1);
+    m.def("conv2d_stem_fwd", &conv2d_stem_fwd,
+          "C < 8 stem forward from the unpadded bf16 x and the fp32 master "
+          "weight: (y, slab); slab is the [2, Ko, S] BN partial slab with "
+          "want_stats, else undefined.  stem as in conv2d_stem_plan",
+          py::arg("x"), py::arg("w"), py::arg("bias") = c10::nullopt,
+          py::arg("stride") = 1, py::arg("pad") = 0,
+          py::arg("want_stats") = false, py::arg("stem") = -1);
+    m.def("conv2d_stem_plan", &conv2d_stem_plan,
+          "'direct' or 'mfma': the kernel conv2d_stem_fwd would run for this "
+          "shape; stem -1 automatic, 0 mfma, 1 forces direct; launches "
+          "nothing",
+          py::arg("N"), py::arg("C"), py::arg("H"), py::arg("W"),
+          py::arg("Ko"), py::arg("R"), py::arg("S"), py::arg("stride"),
+          py::arg("pad"), py::arg("stem") = -1);
     m.def("conv2d_kloop_plan", &conv2d_kloop_plan,
           "'walk' or 'decode': the K loop conv2d_fwd[_stats] (mode 0) or "
           "conv2d_dgrad (mode 1) would run for this shape; kwalk -1 "

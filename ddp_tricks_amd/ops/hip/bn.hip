@@ -59,7 +59,70 @@ __global__ void k_bn_partial(const bf16* __restrict__ x, long M, int C,
     }
 }
 
-// combine: wave per channel; lanes sweep the S splits coalesced
+// Sums of one channel's S slab entries, both halves of a [2][C][S] slab; the
+// summation order is a function of S alone.
+//   S <= BN_NARROW_S (every slab the BN kernels write, bn_splits' cap): a
+//     wave per channel, lanes sweep s = lane, lane+64, ..., then
+//     wave_reduce_sum.
+//   S >  BN_NARROW_S (conv-epilogue slabs, one slice per M-tile): a block of
+//     BN_WIDE_WAVES waves per channel; wave w sweeps the contiguous share
+//     [w*ceil(S/16), (w+1)*ceil(S/16)) the same way, the per-wave totals
+//     meet in LDS and one thread adds them in wave order.
+// combine_geom() below gives the matching launch shape.  Returns true in the
+// one thread per channel that holds the totals; every thread of the block
+// must call it (the wide path has a barrier).
+constexpr int BN_NARROW_S = 1024;
+constexpr int BN_WIDE_WAVES = 16;
+
+DEV_INLINE bool bn_slab_sums(const float* __restrict__ slab, int S, int C,
+                             int& c, float& a, float& b) {
+    __shared__ float part[2][BN_WIDE_WAVES];
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const bool wide = S > BN_NARROW_S;
+    int s0 = lane, s1 = S;
+    if (wide) {
+        c = blockIdx.x;
+        const int share = (S + BN_WIDE_WAVES - 1) / BN_WIDE_WAVES;
+        s0 = wave * share + lane;
+        s1 = min(S, (wave + 1) * share);
+    } else {
+        c = blockIdx.x * (blockDim.x >> 6) + wave;
+    }
+    a = 0.f;
+    b = 0.f;
+    if (c >= C) return false;       // narrow only: the wide grid is C blocks
+    for (int s = s0; s < s1; s += 64) {
+        a += slab[(long)c * S + s];
+        b += slab[(long)C * S + (long)c * S + s];
+    }
+    a = wave_reduce_sum(a);
+    b = wave_reduce_sum(b);
+    if (!wide) return lane == 0;
+    if (lane == 0) {
+        part[0][wave] = a;
+        part[1][wave] = b;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return false;
+    a = 0.f;
+    b = 0.f;
+    #pragma unroll
+    for (int w = 0; w < BN_WIDE_WAVES; ++w) {
+        a += part[0][w];
+        b += part[1][w];
+    }
+    return true;
+}
+
+struct CombineGeom { dim3 grid, block; };
+static inline CombineGeom combine_geom(int S, int C) {
+    const bool wide = S > BN_NARROW_S;
+    return {dim3(wide ? C : ceil_div_i(C, 4)),
+            dim3(wide ? BN_WIDE_WAVES * 64 : 256)};
+}
+
+// combine: bn_slab_sums, then the per-channel coefficients
 __global__ void k_bn_combine(const float* __restrict__ slab, int S, int C,
                              long M, const float* __restrict__ gamma,
                              const float* __restrict__ beta,
@@ -70,17 +133,9 @@ __global__ void k_bn_combine(const float* __restrict__ slab, int S, int C,
                              float* __restrict__ save_invstd,
                              float* __restrict__ scale,
                              float* __restrict__ shift) {
-    int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    int lane = threadIdx.x & 63;
-    if (c >= C) return;
-    float sum = 0.f, sq = 0.f;
-    for (int s = lane; s < S; s += 64) {
-        sum += slab[(long)c * S + s];
-        sq += slab[(long)C * S + (long)c * S + s];
-    }
-    sum = wave_reduce_sum(sum);
-    sq = wave_reduce_sum(sq);
-    if (lane != 0) return;
+    int c;
+    float sum, sq;
+    if (!bn_slab_sums(slab, S, C, c, sum, sq)) return;
     float mean = sum / M;
     float var = fmaxf(sq / M - mean * mean, 0.f);
     float invstd = rsqrtf(var + eps);
@@ -259,17 +314,9 @@ __global__ void k_bn_bwd_combine(const float* __restrict__ slab, int S, int C,
                                  float* __restrict__ coef_a,
                                  float* __restrict__ coef_b,
                                  float* __restrict__ coef_c) {
-    int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    int lane = threadIdx.x & 63;
-    if (c >= C) return;
-    float sum_dy = 0.f, sum_dyx = 0.f;
-    for (int s = lane; s < S; s += 64) {
-        sum_dy += slab[(long)c * S + s];
-        sum_dyx += slab[(long)C * S + (long)c * S + s];
-    }
-    sum_dy = wave_reduce_sum(sum_dy);
-    sum_dyx = wave_reduce_sum(sum_dyx);
-    if (lane != 0) return;
+    int c;
+    float sum_dy, sum_dyx;
+    if (!bn_slab_sums(slab, S, C, c, sum_dy, sum_dyx)) return;
     dgamma[c] = sum_dyx;
     dbeta[c] = sum_dy;
     float g = gamma ? gamma[c] : 1.f;
@@ -361,8 +408,8 @@ __global__ void k_bn_bwd_dx(const bf16* __restrict__ x,
 // (finalize / coefficients: add the gathered rows, then the combine's tail
 // with the GLOBAL row count).  The memory-bound passes are the kernels
 // above, unchanged.  Two properties hold by construction:
-//   * pack repeats the combine's summation order (wave per channel, lanes
-//     sweep s = lane, lane+64, ..., then wave_reduce_sum) and the cross-rank
+//   * pack sums the slab with the combine's own bn_slab_sums (one order at
+//     every slab width) and the cross-rank
 //     add starts from row 0, so with one rank every output is bit-identical
 //     to k_bn_combine / k_bn_bwd_combine;
 //   * every rank adds the same gathered rows in rank order w = 0..W-1, so
@@ -377,17 +424,9 @@ constexpr int SYNC_COUNT_SHIFT = 12;
 // M >= 0 also row[2C], row[2C+1] = the split row count
 __global__ void k_bn_sync_pack(const float* __restrict__ slab, int S, int C,
                                long M, float* __restrict__ row) {
-    int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    int lane = threadIdx.x & 63;
-    if (c >= C) return;
-    float sum = 0.f, sq = 0.f;
-    for (int s = lane; s < S; s += 64) {
-        sum += slab[(long)c * S + s];
-        sq += slab[(long)C * S + (long)c * S + s];
-    }
-    sum = wave_reduce_sum(sum);
-    sq = wave_reduce_sum(sq);
-    if (lane != 0) return;
+    int c;
+    float sum, sq;
+    if (!bn_slab_sums(slab, S, C, c, sum, sq)) return;
     row[c] = sum;
     row[C + c] = sq;
     if (c == 0 && M >= 0) {
@@ -915,7 +954,8 @@ std::vector<at::Tensor> bn_fwd_train(at::Tensor x, at::Tensor gamma,
                            slab.data_ptr<float>());
         HIP_CHECK_LAST();
     }
-    hipLaunchKernelGGL(k_bn_combine, dim3(ceil_div_i(C, 4)), dim3(256), 0,
+    hipLaunchKernelGGL(k_bn_combine, combine_geom(S, C).grid,
+                       combine_geom(S, C).block, 0,
                        stream.stream(), slab.data_ptr<float>(), S, C, M,
                        gamma.data_ptr<float>(), beta.data_ptr<float>(),
                        running_mean.data_ptr<float>(),
@@ -1105,7 +1145,8 @@ std::vector<at::Tensor> bn_bwd(at::Tensor x, at::Tensor dy, at::Tensor gamma,
                            slab.data_ptr<float>());
         HIP_CHECK_LAST();
     }
-    hipLaunchKernelGGL(k_bn_bwd_combine, dim3(ceil_div_i(C, 4)), dim3(256), 0,
+    hipLaunchKernelGGL(k_bn_bwd_combine, combine_geom(S, C).grid,
+                       combine_geom(S, C).block, 0,
                        stream.stream(), slab.data_ptr<float>(), S, C, M,
                        gamma.data_ptr<float>(), save_invstd.data_ptr<float>(),
                        dgamma.data_ptr<float>(), dbeta.data_ptr<float>(),
@@ -1194,7 +1235,8 @@ at::Tensor bn_sync_local(at::Tensor x, c10::optional<at::Tensor> pre_stats) {
                            S, slab.data_ptr<float>());
         HIP_CHECK_LAST();
     }
-    hipLaunchKernelGGL(k_bn_sync_pack, dim3(ceil_div_i(C, 4)), dim3(256), 0,
+    hipLaunchKernelGGL(k_bn_sync_pack, combine_geom(S, C).grid,
+                       combine_geom(S, C).block, 0,
                        stream.stream(), slab.data_ptr<float>(), S, C, M,
                        row.data_ptr<float>());
     HIP_CHECK_LAST();
@@ -1309,7 +1351,8 @@ at::Tensor bn_sync_bwd_local(at::Tensor x, at::Tensor dy,
                        save_invstd.data_ptr<float>(), M, C, S, fuse_relu,
                        slab.data_ptr<float>());
     HIP_CHECK_LAST();
-    hipLaunchKernelGGL(k_bn_sync_pack, dim3(ceil_div_i(C, 4)), dim3(256), 0,
+    hipLaunchKernelGGL(k_bn_sync_pack, combine_geom(S, C).grid,
+                       combine_geom(S, C).block, 0,
                        stream.stream(), slab.data_ptr<float>(), S, C, -1l,
                        row.data_ptr<float>());
     HIP_CHECK_LAST();
@@ -1434,7 +1477,8 @@ std::vector<at::Tensor> bn_fwd_train_pool2(at::Tensor x, at::Tensor gamma,
                            slab.data_ptr<float>());
         HIP_CHECK_LAST();
     }
-    hipLaunchKernelGGL(k_bn_combine, dim3(ceil_div_i(C, 4)), dim3(256), 0,
+    hipLaunchKernelGGL(k_bn_combine, combine_geom(S, C).grid,
+                       combine_geom(S, C).block, 0,
                        stream.stream(), slab.data_ptr<float>(), S, C, M,
                        gamma.data_ptr<float>(), beta.data_ptr<float>(),
                        running_mean.data_ptr<float>(),
@@ -1506,7 +1550,8 @@ std::vector<at::Tensor> bn_bwd_pool2(at::Tensor x, at::Tensor dy_pooled,
                        slab.data_ptr<float>());
     HIP_CHECK_LAST();
     // M, not Mp: coef_b/coef_c are means over the full-resolution rows
-    hipLaunchKernelGGL(k_bn_bwd_combine, dim3(ceil_div_i(C, 4)), dim3(256), 0,
+    hipLaunchKernelGGL(k_bn_bwd_combine, combine_geom(S, C).grid,
+                       combine_geom(S, C).block, 0,
                        stream.stream(), slab.data_ptr<float>(), S, C, M,
                        gamma.data_ptr<float>(), save_invstd.data_ptr<float>(),
                        dgamma.data_ptr<float>(), dbeta.data_ptr<float>(),

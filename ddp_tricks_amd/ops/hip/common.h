@@ -26,6 +26,12 @@ typedef float  f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int WAVE = 64;
 
+// Kernel attribute: no packed fp32 arithmetic (v_pk_fma_f32, v_pk_add_f32,
+// v_pk_mul_f32) in this function; the compiler's op_sel forms of them are
+// not relied on in new kernels.  Not for a kernel whose bits must match an
+// older build: it changes how the compiler contracts a * b + c * d.
+#define NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+
 DEV_INLINE float bf2f(bf16 v) { return __bfloat162float(v); }
 DEV_INLINE bf16 f2bf(float v) { return __float2bfloat16(v); }
 

@@ -734,6 +734,142 @@ __global__ void k_conv_small_cin(const bf16* __restrict__ x,
     }
 }
 
+// Direct stem forward (C == 1, 3x3, stride 1, pad 0 or 1, Ko % 8 == 0,
+// Ko <= 64): the forward sibling of k_wgrad_c1_r3_stream.  The MFMA path
+// pads C to 8, so 7/8 of its contraction is zeros, and needs a padded copy
+// of x and a packed weight image; this kernel reads the unpadded x and the
+// fp32 master weight (rounded to bf16 here, f2us like k_pack_conv_weight)
+// and is bounded by the y write.
+//   * A work unit is one band of BP output rows of one image.  The block
+//     copies the band's BP + 2 input rows into LDS as fp32 with a zero
+//     border of `pad`, so the window reads need no bounds test and x is
+//     converted once per element.
+//   * A lane owns the 8-channel group cg = lane % (Ko/8) for its whole life:
+//     its 9 x 8 weights and 8 biases sit in registers (compile-time indices
+//     only).  One wave store covers RPL = 64 / (Ko/8) consecutive pixels as
+//     16-B chunks (1 KiB contiguous at Ko = 64); the block steps 4 * RPL
+//     pixels per trip and a lane carries (q, LDS index) incrementally — no
+//     division in the pixel loop.
+//   * v = fmaf chain over the taps in (r, s) order from 0, + bias, bf16 RNE.
+//   * STATS: per-lane fp32 sum / sumsq of v (pre-rounding, like the GEMM
+//     epilogue's psum / psq) over all of the block's units; at the end
+//     thread c < Ko adds the 4 waves x RPL rows of channel c in index order
+//     and writes slab[c][block], slab[Ko + c][block] — every block writes
+//     its slot, lanes without pixels contribute zeros.
+// The grid is min(STEM_MAX_BLOCKS, units, ceil(N*P*Q / 128)): a function of
+// the shape alone, and every block has at least one unit.
+// fp32 -> bf16 RNE on the hardware convert (v_cvt_pk_bf16_f32): the bits of
+// f2us for every finite input, at a fifth of its instructions
+DEV_INLINE short f2bf_bits(float f) {
+    return __builtin_bit_cast(short, (__bf16)f);
+}
+
+constexpr int STEM_MAX_BLOCKS = 1024;
+constexpr int STEM_LDS_FLOATS = 4096;      // band image cap, 16 KiB
+
+template <bool BIAS, bool STATS>
+__global__ __launch_bounds__(256) NO_PK_F32
+void k_conv_c1_r3_fwd(const bf16* __restrict__ x, const float* __restrict__ w,
+                      const float* __restrict__ bias, bf16* __restrict__ y,
+                      float* __restrict__ slab, ConvShape cs, int BP,
+                      int nbands) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* img = reinterpret_cast<float*>(smem);    // [BP + 2][LW]
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int lpr = cs.Ko >> 3;            // lanes per pixel
+    const int rpl = 64 / lpr;              // pixels per wave store
+    const int r_in = lane / lpr;
+    const int cg = lane - r_in * lpr;
+    const bool lane_on = r_in < rpl;
+    const int LW = cs.W + 2 * cs.pad;
+    const unsigned short* xs = reinterpret_cast<const unsigned short*>(x);
+
+    float wr[9][8], bv[8];
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        #pragma unroll
+        for (int k = 0; k < 9; ++k)
+            wr[k][j] = us2f(f2us(w[(cg * 8 + j) * 9 + k]));
+        bv[j] = BIAS ? bias[cg * 8 + j] : 0.f;
+    }
+    // one trip moves a lane 4 * rpl pixels on: dp rows and dq columns
+    const int step = 4 * rpl;
+    const int dp = step / cs.Q, dq = step - dp * cs.Q;
+    const int dli = dp * LW + dq;
+    const int units = cs.N * nbands;
+    float sum[8] = {}, sq[8] = {};
+
+    for (int u = blockIdx.x; u < units; u += gridDim.x) {
+        const int n = u / nbands;
+        const int p0 = (u - n * nbands) * BP;
+        const int bpc = min(BP, cs.P - p0);
+        __syncthreads();                    // the previous unit's reads
+        for (int row = wave; row < bpc + 2; row += 4) {
+            const int h = p0 + row - cs.pad;
+            for (int col = lane; col < LW; col += 64) {
+                const int wc = col - cs.pad;
+                const bool inb = h >= 0 && h < cs.H && wc >= 0 && wc < cs.W;
+                img[row * LW + col] =
+                    inb ? us2f(xs[((long)n * cs.H + h) * cs.W + wc]) : 0.f;
+            }
+        }
+        __syncthreads();
+        const int npix = bpc * cs.Q;
+        const long ybase = ((long)n * cs.P + p0) * cs.Q;
+        int pix = lane_on ? wave * rpl + r_in : npix;
+        const int pp = (int)fd_div((unsigned)pix, cs.fdQ);
+        int q = pix - pp * cs.Q;
+        int li = pp * LW + q;
+        for (; pix < npix; pix += step) {
+            float xw[9];
+            #pragma unroll
+            for (int r = 0; r < 3; ++r)
+                #pragma unroll
+                for (int s = 0; s < 3; ++s)
+                    xw[r * 3 + s] = img[li + r * LW + s];
+            bf16x8_t o;
+            #pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                float v = 0.f;
+                #pragma unroll
+                for (int k = 0; k < 9; ++k) v = fmaf(xw[k], wr[k][j], v);
+                if (BIAS) v += bv[j];
+                if (STATS) {
+                    sum[j] += v;
+                    sq[j] = fmaf(v, v, sq[j]);
+                }
+                o[j] = f2bf_bits(v);
+            }
+            *reinterpret_cast<bf16x8_t*>(&y[(ybase + pix) * cs.Ko + cg * 8]) = o;
+            q += dq;
+            li += dli;
+            if (q >= cs.Q) {
+                q -= cs.Q;
+                li += LW - cs.Q;
+            }
+        }
+    }
+    if constexpr (STATS) {
+        __shared__ float red[8][256 + 8];   // +8: reader banks rj*8 + rc distinct
+        const int rc = tid >> 3, rj = tid & 7;   // reader: channel rc*8 + rj
+        #pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            __syncthreads();
+            #pragma unroll
+            for (int j = 0; j < 8; ++j) red[j][tid] = h ? sq[j] : sum[j];
+            __syncthreads();
+            if (tid < cs.Ko) {
+                float t = 0.f;
+                for (int wv = 0; wv < 4; ++wv)
+                    for (int r = 0; r < rpl; ++r)
+                        t += red[rj][wv * 64 + r * lpr + rc];
+                slab[((long)h * cs.Ko + tid) * gridDim.x + blockIdx.x] = t;
+            }
+        }
+    }
+}
+
 // -------------------------------------------------------- backward weight ---
 
 // Every MFMA leaf writes slab[s][ko, rsc] = Σ_{m in split s} dy[m][ko] ·
@@ -1807,6 +1943,108 @@ std::vector<at::Tensor> conv2d_fwd_stats(at::Tensor x, at::Tensor w,
                                          c10::optional<at::Tensor> bias,
                                          long stride, long pad, long kwalk) {
     return conv_fwd_impl(x, w, bias, stride, pad, true, kwalk);
+}
+
+at::Tensor pad8_channels(at::Tensor x);                       // elementwise.hip
+std::vector<at::Tensor> pack_conv_weight(at::Tensor w, bool pad8,
+                                         bool want_wt2);
+
+// DDPX_STEM, read once per process: "0" keeps the automatic plan on the MFMA
+// path (A/B runs)
+static bool stem_env_off() {
+    static const char* v = getenv("DDPX_STEM");
+    return v && v[0] == '0' && v[1] == 0;
+}
+
+// Stem forward: "direct" (k_conv_c1_r3_fwd) or "mfma" (channels padded to
+// 8, k_conv_gemm).  The one place that decides; pure host arithmetic.  stem:
+// -1 automatic, 0 mfma, 1 forces direct; a forced direct on a shape it does
+// not fit runs mfma, and the plan says so.  Direct fits C == 1, 3x3,
+// stride 1, pad 0 or 1, Ko % 8 == 0, Ko <= 64 (a lane's 8-channel group in
+// 64 lanes), and a row of x plus borders narrow enough that a one-row band
+// fits the kernel's LDS image.
+static const char* plan_stem(const ConvShape& cs, long stem) {
+    TORCH_CHECK(stem >= -1 && stem <= 1, "conv stem must be -1 (automatic), "
+                "0 (mfma) or 1 (direct); got ", stem);
+    const bool fits = cs.C == 1 && cs.R == 3 && cs.S == 3 && cs.stride == 1 &&
+                      (cs.pad == 0 || cs.pad == 1) && cs.Ko % 8 == 0 &&
+                      cs.Ko <= 64 && cs.P >= 1 && cs.Q >= 1 &&
+                      3 * (cs.W + 2 * cs.pad) <= STEM_LDS_FLOATS;
+    if (!fits || stem == 0 || (stem == -1 && stem_env_off())) return "mfma";
+    // Automatic is the fit rule: the direct kernel does 1/8 of the MFMA
+    // path's multiplies and skips its two helper launches at every shape it
+    // fits (tools/bench_kernels.py --stem, docs/KERNELS.md).
+    return "direct";
+}
+
+std::string conv2d_stem_plan(long N, long C, long H, long W, long Ko, long R,
+                             long S, long stride, long pad, long stem) {
+    TORCH_CHECK(N >= 1 && C >= 1 && Ko >= 1 && R >= 1 && S >= 1 &&
+                stride >= 1 && pad >= 0 && H + 2 * pad >= R &&
+                W + 2 * pad >= S, "conv2d_stem_plan: bad shape");
+    ConvShape cs = make_shape((int)N, (int)C, (int)H, (int)W, (int)Ko, (int)R,
+                              (int)S, (int)stride, (int)pad);
+    return plan_stem(cs, stem);
+}
+
+// x: bf16 [N,C,H,W] channels_last, C < 8 unpadded; w: the fp32 master
+// [Ko,C,R,S].  Returns (y, slab); slab is [2][Ko][S] with want_stats, else
+// undefined.  On "mfma" the padded x and the packed weight are made here.
+std::tuple<at::Tensor, at::Tensor> conv2d_stem_fwd(
+        at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias,
+        long stride, long pad, bool want_stats, long stem) {
+    TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
+                x.dim() == 4, "conv2d_stem_fwd: x must be bf16 [N,C,H,W]");
+    TORCH_CHECK(w.is_cuda() && w.scalar_type() == at::kFloat && w.dim() == 4 &&
+                w.is_contiguous() && w.size(1) == x.size(1),
+                "conv2d_stem_fwd: w must be the contiguous fp32 [Ko,C,R,S]");
+    TORCH_CHECK(x.size(1) < 8, "conv2d_stem_fwd: C < 8 only");
+    TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast),
+                "conv2d_stem_fwd: x must be channels_last");
+    if (bias.has_value())
+        TORCH_CHECK(bias->is_cuda() && bias->scalar_type() == at::kFloat &&
+                    bias->is_contiguous() && bias->numel() == w.size(0),
+                    "conv2d_stem_fwd: bias must be fp32 [Ko]");
+    TORCH_CHECK(stride >= 1 && pad >= 0 && x.size(2) + 2 * pad >= w.size(2) &&
+                x.size(3) + 2 * pad >= w.size(3),
+                "conv2d_stem_fwd: bad stride / pad");
+    ConvShape cs = make_shape(x, w.size(0), w.size(2), w.size(3), (int)stride,
+                              (int)pad);
+    if (plan_stem(cs, stem)[0] == 'm') {
+        auto out = conv_fwd_impl(pad8_channels(x),
+                                 pack_conv_weight(w, true, false)[0], bias,
+                                 stride, pad, want_stats, -1);
+        return {out[0], out[1]};
+    }
+    const int LW = cs.W + 2 * cs.pad;
+    const int BP = std::min(cs.P, STEM_LDS_FLOATS / LW - 2);
+    const int nbands = ceil_div_i(cs.P, BP);
+    const long units = (long)cs.N * nbands;
+    TORCH_CHECK(units < INT_MAX, "conv2d_stem_fwd: too many row bands");
+    // no more blocks than 128-pixel tiles of the MFMA path (a small shape
+    // gets the slab width it always had), than units, or than the cap
+    const long M = (long)cs.N * cs.P * cs.Q;
+    const int blocks = (int)std::min<long>(
+        {(long)STEM_MAX_BLOCKS, units, (M + CBM - 1) / CBM});
+    auto y = empty_nhwc(x, cs.N, cs.Ko, cs.P, cs.Q);
+    at::Tensor slab;
+    if (want_stats)
+        slab = at::empty({2, (long)cs.Ko, (long)blocks},
+                         x.options().dtype(at::kFloat));
+    const bool hb = bias.has_value();
+    auto kern = want_stats
+        ? (hb ? k_conv_c1_r3_fwd<true, true> : k_conv_c1_r3_fwd<false, true>)
+        : (hb ? k_conv_c1_r3_fwd<true, false> : k_conv_c1_r3_fwd<false, false>);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), (BP + 2) * LW * 4,
+                       at::hip::getCurrentHIPStream().stream(),
+                       reinterpret_cast<const bf16*>(x.data_ptr()),
+                       w.data_ptr<float>(),
+                       hb ? bias->data_ptr<float>() : nullptr,
+                       reinterpret_cast<bf16*>(y.data_ptr()),
+                       want_stats ? slab.data_ptr<float>() : nullptr, cs, BP,
+                       nbands);
+    HIP_CHECK_LAST();
+    return {y, slab};
 }
 
 // dy: NCHW logical / channels_last bf16 [N,Ko,P,Q]; wt2: [C, R*S*Ko] bf16

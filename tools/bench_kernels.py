@@ -7,6 +7,7 @@ Usage (on a GPU box):  python tools/bench_kernels.py [--resnet]
                        python tools/bench_kernels.py --wgraddma [--leaves wt3]
                        python tools/bench_kernels.py --dgradtaps
                        python tools/bench_kernels.py --kwalk
+                       python tools/bench_kernels.py --stem
 
 Times conv fwd/dgrad/wgrad per shape with HIP events (200 reps after 20
 warmup) and prints achieved TFLOP/s next to microseconds, so kernel A/B
@@ -502,6 +503,85 @@ def bench_kwalk(rounds):
         torch.cuda.empty_cache()
 
 
+def _wide_slab_rows(ext, rounds):
+    """bn_fwd_train behind a conv-epilogue slab, one slice per 128-row
+    M-tile: Toy_Net's BN1 (C = 64, S = 5408) and BN2 (C = 128, S = 4608) at
+    B = 1024.  The call is the combine plus the apply pass."""
+    dev = torch.device("cuda:0")
+    print(f"{'op':14s} {'C':>4s} {'S':>5s} {'med us':>9s} {'min':>9s} "
+          f"{'max':>9s}")
+    for C, HW in ((64, 26), (128, 24)):
+        M = 1024 * HW * HW
+        S = (M + 127) // 128
+        g = torch.Generator(device=dev).manual_seed(0)
+        x = torch.randn(1024, C, HW, HW, device=dev, generator=g) \
+            .to(torch.bfloat16).contiguous(memory_format=CL)
+        slab = torch.rand(2, C, S, device=dev, generator=g) * 128.0
+        slab[1] += 128.0
+        gamma = torch.ones(C, device=dev)
+        beta = torch.zeros(C, device=dev)
+        rm, rv = torch.zeros(C, device=dev), torch.ones(C, device=dev)
+
+        def call():
+            return ext.bn_fwd_train(x, gamma, beta, rm, rv, 0.1, 1e-5, True,
+                                    None, slab)
+        res = _time_alternating({"bn": call}, rounds=rounds, warmup=30)
+        med, lo, hi = res["bn"]
+        print(f"{'bn_fwd_train':14s} {C:4d} {S:5d} {med:9.1f} {lo:9.1f} "
+              f"{hi:9.1f}", flush=True)
+        del x, slab
+        torch.cuda.empty_cache()
+
+
+def bench_stem(rounds):
+    """Toy_Net's stem (1 -> 64 channels, 3x3, 28x28, B = 1024) through
+    conv2d_stem_fwd with statistics: the MFMA path on channels padded to 8
+    (stem 0: pad kernel, weight pack and implicit GEMM, what a training step
+    launches) against the direct kernel (stem 1), alternated in one process
+    (`stem` is an argument).  y and the float64 slab totals are checked
+    against the MFMA path before timing; 30 warm-up calls, then device
+    events around 10 calls, median/min/max over `rounds`.  GB/s is the
+    88.6 MB y write over the median.  Then the wide-slab BN rows."""
+    ext = load_extension(required=True)
+    dev = torch.device("cuda:0")
+    N, C, H, W, K, R, stride, pad = 1024, 1, 28, 28, 64, 3, 1, 0
+    P = H - 2
+    g = torch.Generator(device=dev).manual_seed(0)
+    x = torch.randn(N, C, H, W, device=dev, generator=g) \
+        .to(torch.bfloat16).contiguous(memory_format=CL)
+    w = torch.randn(K, C, R, R, device=dev, generator=g) / 3.0
+    b = torch.randn(K, device=dev, generator=g)
+
+    def call(stem):
+        return ext.conv2d_stem_fwd(x, w, b, stride, pad, True, stem)
+    (y0, s0), (y1, s1) = call(0), call(1)
+    # the two paths add the nine products in different orders: y may differ
+    # by one bf16 ulp where v sits on a rounding boundary, nowhere by more
+    d = (y1.float() - y0.float()).abs()
+    ulp = y0.float().abs().clamp(min=2.0 ** -126) * 2.0 ** -7
+    if not bool((d <= ulp).all()):
+        raise RuntimeError("stem: direct differs from mfma by more than "
+                           "one bf16 ulp")
+    t0, t1 = s0.double().sum(2), s1.double().sum(2)
+    if not torch.allclose(t1, t0, rtol=1e-4, atol=1e-2):
+        raise RuntimeError("stem: slab totals differ")
+    print(f"y: {float((d > 0).float().mean()) * 100:.3f} % of elements differ "
+          f"(each by one bf16 ulp at most); slab totals agree to 1e-4")
+    ybytes = N * P * P * K * 2
+    print(f"{'stem':>4s} {'plan':7s} {'med us':>9s} {'min':>9s} {'max':>9s} "
+          f"{'vs mfma':>8s} {'y GB/s':>8s}")
+    res = _time_alternating({st: (lambda st=st: call(st)) for st in (0, 1)},
+                            rounds=rounds, warmup=30)
+    for st in (0, 1):
+        med, lo, hi = res[st]
+        plan = ext.conv2d_stem_plan(N, C, H, W, K, R, R, stride, pad, st)
+        print(f"{st:4d} {plan:7s} {med:9.1f} {lo:9.1f} {hi:9.1f} "
+              f"{med / res[0][0]:8.3f} {ybytes / med / 1e3:8.0f}", flush=True)
+    del x, y0, y1
+    torch.cuda.empty_cache()
+    _wide_slab_rows(ext, rounds)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clip", action="store_true")
@@ -517,6 +597,7 @@ def main():
                     help="conv2d_dgrad group values for --dgradtaps, raster "
                          "(0) first")
     ap.add_argument("--kwalk", action="store_true")
+    ap.add_argument("--stem", action="store_true")
     ap.add_argument("--resnet", action="store_true")
     ap.add_argument("--functional", action="store_true")
     ap.add_argument("--bn", action="store_true")
@@ -541,6 +622,9 @@ def main():
         return
     if args.kwalk:
         bench_kwalk(rounds=30)
+        return
+    if args.stem:
+        bench_stem(rounds=30)
         return
     if args.bn:
         bench_bn(args.reps)
