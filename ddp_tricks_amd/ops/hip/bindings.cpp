@@ -122,15 +122,17 @@ std::vector<at::Tensor> bn_sync_bwd_dx(at::Tensor x, at::Tensor dy,
 
 // gemm.hip
 at::Tensor gemm_tn(at::Tensor A, at::Tensor B, c10::optional<at::Tensor> bias,
-                   bool out_f32);
+                   bool out_f32, long impl);
 at::Tensor transpose_bf16(at::Tensor x);
 at::Tensor col_sum(at::Tensor x);
-at::Tensor linear_fwd(at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias);
-at::Tensor linear_dgrad(at::Tensor dy, at::Tensor w);
-at::Tensor linear_wgrad(at::Tensor dy, at::Tensor x);
+at::Tensor linear_fwd(at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias,
+                      long impl);
+at::Tensor linear_dgrad(at::Tensor dy, at::Tensor w, long impl);
+at::Tensor linear_wgrad(at::Tensor dy, at::Tensor x, long impl);
 at::Tensor linear_act_fwd(at::Tensor x, at::Tensor w,
                           c10::optional<at::Tensor> bias, long thr,
-                          double scale, long call_seed);
+                          double scale, long call_seed, long impl);
+std::string linear_plan(long op, long M, long N, long K, long impl);
 at::Tensor relu_drop_bwd(at::Tensor dy, at::Tensor y, double scale);
 
 // conv.hip
@@ -311,19 +313,29 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("gathered"), py::arg("count"),
           py::arg("want_dresid") = false);
     m.def("gemm_tn", &gemm_tn, py::arg("A"), py::arg("B"),
-          py::arg("bias") = c10::nullopt, py::arg("out_f32") = false);
+          py::arg("bias") = c10::nullopt, py::arg("out_f32") = false,
+          py::arg("impl") = -1);
     m.def("transpose_bf16", &transpose_bf16);
     m.def("col_sum", &col_sum);
     m.def("linear_fwd", &linear_fwd, py::arg("x"), py::arg("w"),
-          py::arg("bias") = c10::nullopt);
-    m.def("linear_dgrad", &linear_dgrad);
-    m.def("linear_wgrad", &linear_wgrad);
+          py::arg("bias") = c10::nullopt, py::arg("impl") = -1);
+    m.def("linear_dgrad", &linear_dgrad, py::arg("dy"), py::arg("w"),
+          py::arg("impl") = -1);
+    m.def("linear_wgrad", &linear_wgrad, py::arg("dy"), py::arg("x"),
+          py::arg("impl") = -1);
+    m.def("linear_plan", &linear_plan,
+          "'dma' or 'legacy': the GEMM a linear layer's product would run; "
+          "op 0 forward, 1 dgrad, 2 wgrad, 3 a plain gemm_tn(A [M,K], B [N,K]); "
+          "(M, N, K) = batch, out features, in features; impl -1 automatic, 0 legacy, 1 forces the LDS-DMA "
+          "kernel where the shape fits; launches nothing",
+          py::arg("op"), py::arg("M"), py::arg("N"), py::arg("K"),
+          py::arg("impl") = -1);
     m.def("linear_act_fwd", &linear_act_fwd,
           "bf16 dropout(relu(x w^T + bias)) in the GEMM epilogue; thr is the "
           "drop probability in 1/65536 (0: ReLU alone), scale = "
           "65536/(65536-thr), call_seed the per-call seed's 64 bits as int64",
           py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("thr"),
-          py::arg("scale"), py::arg("call_seed"));
+          py::arg("scale"), py::arg("call_seed"), py::arg("impl") = -1);
     m.def("relu_drop_bwd", &relu_drop_bwd,
           "dz = dy*scale where the fused forward's output y > 0, else 0",
           py::arg("dy"), py::arg("y"), py::arg("scale"));

@@ -8,6 +8,7 @@ Usage (on a GPU box):  python tools/bench_kernels.py [--resnet]
                        python tools/bench_kernels.py --dgradtaps
                        python tools/bench_kernels.py --kwalk
                        python tools/bench_kernels.py --stem
+                       python tools/bench_kernels.py --linear
 
 Times conv fwd/dgrad/wgrad per shape with HIP events (200 reps after 20
 warmup) and prints achieved TFLOP/s next to microseconds, so kernel A/B
@@ -503,6 +504,49 @@ def bench_kwalk(rounds):
         torch.cuda.empty_cache()
 
 
+def bench_linear(rounds):
+    """The linear layers' three products through their whole entry points
+    (transposes and slab combines included): the legacy path (impl 0)
+    against the LDS-DMA kernel (impl 1), alternated in one process (`impl`
+    is an argument).  Shapes: Toy_Net's Linear(8192, 512) at B = 1024,
+    VGG-16's Linear(25088, 4096) and Linear(4096, 4096) at B = 256.  Outputs
+    are checked equal before timing; 30 warm-up calls, then device events
+    around 10 calls, median/min/max over `rounds`."""
+    ext = load_extension(required=True)
+    dev = torch.device("cuda:0")
+    shapes = [("toy fc1", 1024, 512, 8192), ("vgg fc1", 256, 4096, 25088),
+              ("vgg fc2", 256, 4096, 4096)]
+    print(f"{'layer':8s} {'op':6s} {'impl':>4s} {'plan':7s} {'auto':7s} "
+          f"{'med us':>9s} {'min':>9s} {'max':>9s} {'vs legacy':>9s} "
+          f"{'TFLOP/s':>8s}")
+    for name, M, N, K in shapes:
+        g = torch.Generator(device=dev).manual_seed(0)
+        x = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
+        w = (torch.randn(N, K, device=dev, generator=g) / 64) \
+            .to(torch.bfloat16)
+        dy = torch.randn(M, N, device=dev, generator=g).to(torch.bfloat16)
+        b = torch.randn(N, device=dev, generator=g)
+        calls = [("fwd", 0, lambda i: ext.linear_fwd(x, w, b, i)),
+                 ("dgrad", 1, lambda i: ext.linear_dgrad(dy, w, i)),
+                 ("wgrad", 2, lambda i: ext.linear_wgrad(dy, x, i))]
+        flops = 2.0 * M * N * K
+        for op, code, call in calls:
+            if not torch.equal(call(0), call(1)):
+                raise RuntimeError(f"{name} {op}: dma differs from legacy")
+            res = _time_alternating({i: (lambda i=i: call(i))
+                                     for i in (0, 1)}, rounds=rounds,
+                                    warmup=30)
+            for i in (0, 1):
+                med, lo, hi = res[i]
+                print(f"{name:8s} {op:6s} {i:4d} "
+                      f"{ext.linear_plan(code, M, N, K, i):7s} "
+                      f"{ext.linear_plan(code, M, N, K):7s} {med:9.1f} "
+                      f"{lo:9.1f} {hi:9.1f} {med / res[0][0]:9.3f} "
+                      f"{flops / med / 1e6:8.1f}", flush=True)
+        del x, w, dy
+        torch.cuda.empty_cache()
+
+
 def _wide_slab_rows(ext, rounds):
     """bn_fwd_train behind a conv-epilogue slab, one slice per 128-row
     M-tile: Toy_Net's BN1 (C = 64, S = 5408) and BN2 (C = 128, S = 4608) at
@@ -598,6 +642,7 @@ def main():
                          "(0) first")
     ap.add_argument("--kwalk", action="store_true")
     ap.add_argument("--stem", action="store_true")
+    ap.add_argument("--linear", action="store_true")
     ap.add_argument("--resnet", action="store_true")
     ap.add_argument("--functional", action="store_true")
     ap.add_argument("--bn", action="store_true")
@@ -625,6 +670,9 @@ def main():
         return
     if args.stem:
         bench_stem(rounds=30)
+        return
+    if args.linear:
+        bench_linear(rounds=30)
         return
     if args.bn:
         bench_bn(args.reps)
