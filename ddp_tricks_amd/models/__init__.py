@@ -1,3 +1,4 @@
+from .mobilenet import mobilenet_v1  # noqa: F401
 from .resnet import resnet18, resnet34, resnet50  # noqa: F401
 from .toy_net import Toy_Net  # noqa: F401
 from .vgg import vgg16_bn  # noqa: F401
@@ -8,6 +9,7 @@ _REGISTRY = {
     "resnet34": resnet34,
     "resnet50": resnet50,
     "vgg16": vgg16_bn,
+    "mobilenet_v1": mobilenet_v1,
 }
 
 

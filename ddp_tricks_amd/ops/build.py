@@ -28,6 +28,7 @@ SOURCES = [
     "bn.hip",
     "gemm.hip",
     "conv.hip",
+    "dwconv.hip",
     "data.hip",
 ]
 

@@ -356,10 +356,103 @@ def _uniform(v, name):
     return v
 
 
-def conv2d(x, weight, bias=None, stride=1, padding=0):
+# ------------------------------------------------------- depthwise conv2d ---
+
+DW_SCOPE = ("groups == C_in == C_out (channel multiplier 1) with a 3x3 "
+            "kernel, dilation 1, one stride of 1 or 2 and one padding of 0 "
+            "or 1 for both dims, C % 8 == 0 and an fp32 weight")
+
+
+def _dw_in_scope(x, weight, stride, padding, groups, dilation) -> bool:
+    """Whether the depthwise HIP kernels (hip/dwconv.hip) serve this conv."""
+    C = x.shape[1]
+    return (groups == C and dilation == 1
+            and tuple(weight.shape) == (C, 1, 3, 3)
+            and weight.dtype == torch.float32 and C % 8 == 0
+            and stride in (1, 2) and padding in (0, 1))
+
+
+def _dw_fwd(ctx, x, weight, bias, stride, padding, want_stats):
+    """Depthwise forward from the bf16 x and the fp32 master weight: no
+    packed weight image, so nothing enters the weight_variant cache."""
+    ext = require_ext_for(x)
+    xb = _chlast(_to_bf16(x))
+    y, stats = ext.dwconv2d_fwd(
+        xb, weight.detach().contiguous(),
+        bias if bias is None else bias.detach().float().contiguous(),
+        stride, padding, want_stats)
+    ctx.save_for_backward(xb, weight)
+    ctx.meta = (stride, padding, x.dtype, bias is not None)
+    return y, stats
+
+
+def _dw_bwd(ctx, dy):
+    xb, weight = ctx.saved_tensors
+    stride, padding, x_dtype, has_bias = ctx.meta
+    ext = require_ext_for(dy)
+    dyb = _chlast(_to_bf16(dy))
+    dx = dw = db = None
+    if ctx.needs_input_grad[0]:
+        dx = ext.dwconv2d_dgrad(dyb, weight.detach().contiguous(),
+                                xb.shape[2], xb.shape[3], stride, padding)
+        if x_dtype == torch.float32:
+            dx = dx.float()
+    want_db = has_bias and ctx.needs_input_grad[2]
+    # with both gradients wanted the bias sums ride in the wgrad kernel,
+    # which holds every dy element anyway
+    fuse_db = want_db and ctx.needs_input_grad[1]
+    if ctx.needs_input_grad[1]:
+        dw, dbf = ext.dwconv2d_wgrad(dyb, xb, stride, padding, fuse_db)
+        if fuse_db:
+            db = dbf
+    if want_db and not fuse_db:
+        db = ext.col_sum(_nhwc_2d(dyb))
+    return dx, dw, db
+
+
+class _HIPDWConv2d(torch.autograd.Function):
+    """Depthwise 3x3 conv on the direct kernels (see _dw_in_scope)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, padding):
+        return _dw_fwd(ctx, x, weight, bias, stride, padding, False)[0]
+
+    @staticmethod
+    def backward(ctx, dy):
+        dx, dw, db = _dw_bwd(ctx, dy)
+        return dx, dw, db, None, None
+
+
+class _HIPDWConv2dStats(torch.autograd.Function):
+    """_HIPDWConv2d that also emits the consuming BN's partial statistics
+    (non-differentiable), like _HIPConv2dStats."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, padding):
+        y, stats = _dw_fwd(ctx, x, weight, bias, stride, padding, True)
+        ctx.mark_non_differentiable(stats)
+        return y, stats
+
+    @staticmethod
+    def backward(ctx, dy, dstats):
+        dx, dw, db = _dw_bwd(ctx, dy)
+        return dx, dw, db, None, None
+
+
+def conv2d(x, weight, bias=None, stride=1, padding=0, groups=1, dilation=1):
     if x.is_cuda and require_ext_for(x) is not None:
         stride = _uniform(stride, "stride")
         padding = _uniform(padding, "padding")
+        dilation = _uniform(dilation, "dilation")
+        if groups != 1 or dilation != 1:
+            if _dw_in_scope(x, weight, stride, padding, groups, dilation):
+                return _HIPDWConv2d.apply(x, weight, bias, stride, padding)
+            raise ValueError(
+                f"HIP conv2d: groups={groups}, dilation={dilation} with "
+                f"weight {tuple(weight.shape)}, stride={stride}, "
+                f"padding={padding} is not supported; besides dense convs "
+                f"(groups=1, dilation=1) the kernels serve depthwise convs: "
+                f"{DW_SCOPE}")
         # NOTE: a 1x1-as-GEMM route through the linear kernels was tried and
         # REVERTED — measured 2.6 ms vs 0.27 ms for the conv path at
         # ResNet-50's [M~800k, 64x64] shapes (the GEMM ladder's split-K is
@@ -368,8 +461,8 @@ def conv2d(x, weight, bias=None, stride=1, padding=0):
     if x.is_cuda and amp_mod.is_enabled():  # explicit torch-fallback bring-up path
         return F.conv2d(_to_bf16(x), bf16_weight(weight).view_as(weight),
                         bias.to(torch.bfloat16) if bias is not None else None,
-                        stride, padding)
-    return F.conv2d(x, weight, bias, stride, padding)
+                        stride, padding, dilation, groups)
+    return F.conv2d(x, weight, bias, stride, padding, dilation, groups)
 
 
 # ----------------------------------------------------------------- linear ---
@@ -1350,11 +1443,20 @@ def conv_bn(conv_mod, bn_mod, x, residual=None, pool=None):
                  and bn_mod.training and getattr(conv_mod, "dilation",
                                                  (1, 1)) in ((1, 1), 1))
     stats = None
+    groups = getattr(conv_mod, "groups", 1)
+    if use_stats and groups != 1:
+        # a depthwise conv in the direct kernels' scope emits the slab too;
+        # any other grouped conv goes through conv_mod and is refused there
+        use_stats = _dw_in_scope(x, conv_mod.weight,
+                                 _uniform(conv_mod.stride, "stride"),
+                                 _uniform(conv_mod.padding, "padding"),
+                                 groups, 1)
     if use_stats:
         stride = _uniform(conv_mod.stride, "stride")
         padding = _uniform(conv_mod.padding, "padding")
-        y, stats = _HIPConv2dStats.apply(x, conv_mod.weight, conv_mod.bias,
-                                         stride, padding)
+        fn = _HIPConv2dStats if groups == 1 else _HIPDWConv2dStats
+        y, stats = fn.apply(x, conv_mod.weight, conv_mod.bias, stride,
+                            padding)
     else:
         y = conv_mod(x)
     if (pool is not None and residual is None

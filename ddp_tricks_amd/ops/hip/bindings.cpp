@@ -171,6 +171,20 @@ std::tuple<std::string, long, bool> conv2d_wgrad_plan(
     long N, long C, long H, long W, long Ko, long R, long S, long stride,
     long pad, bool want_bias);
 
+// dwconv.hip
+std::tuple<at::Tensor, at::Tensor> dwconv2d_fwd(
+    at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias, long stride,
+    long pad, bool want_stats, long tr);
+at::Tensor dwconv2d_dgrad(at::Tensor dy, at::Tensor w, long H, long W,
+                          long stride, long pad, long tr);
+std::tuple<at::Tensor, at::Tensor> dwconv2d_wgrad(at::Tensor dy, at::Tensor x,
+                                                  long stride, long pad,
+                                                  bool want_db, long tr);
+std::tuple<long, long, long, long> dwconv2d_plan(std::string op, long N,
+                                                 long C, long H, long W,
+                                                 long stride, long pad,
+                                                 long tr);
+
 // data.hip
 std::vector<at::Tensor> batch_gather_aug(at::Tensor store, at::Tensor labels,
                                          at::Tensor index, at::Tensor lut,
@@ -378,6 +392,31 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("N"), py::arg("C"), py::arg("H"), py::arg("W"),
           py::arg("Ko"), py::arg("R"), py::arg("S"), py::arg("stride"),
           py::arg("pad"), py::arg("stem") = -1);
+    m.def("dwconv2d_fwd", &dwconv2d_fwd,
+          "depthwise 3x3 forward from bf16 channels_last x and the fp32 "
+          "master weight [C,1,3,3]: (y, slab); slab is the [2, C, S] BN "
+          "partial slab with want_stats, else undefined",
+          py::arg("x"), py::arg("w"), py::arg("bias") = c10::nullopt,
+          py::arg("stride") = 1, py::arg("pad") = 0,
+          py::arg("want_stats") = false, py::arg("tr") = -1);
+    m.def("dwconv2d_dgrad", &dwconv2d_dgrad,
+          "depthwise 3x3 backward-data: dx bf16 [N,C,H,W], every element "
+          "written",
+          py::arg("dy"), py::arg("w"), py::arg("H"), py::arg("W"),
+          py::arg("stride") = 1, py::arg("pad") = 0, py::arg("tr") = -1);
+    m.def("dwconv2d_wgrad", &dwconv2d_wgrad,
+          "depthwise 3x3 backward-weight: (dw fp32 [C,1,3,3], db fp32 [C] or "
+          "undefined)",
+          py::arg("dy"), py::arg("x"), py::arg("stride") = 1,
+          py::arg("pad") = 0, py::arg("want_db") = false,
+          py::arg("tr") = -1);
+    m.def("dwconv2d_plan", &dwconv2d_plan,
+          "(slice width in chunks, strip rows, grid x, grid y) of the "
+          "depthwise kernel for op 'fwd', 'dgrad' or 'wgrad' over an "
+          "[N,C,H,W] input; launches nothing",
+          py::arg("op"), py::arg("N"), py::arg("C"), py::arg("H"),
+          py::arg("W"), py::arg("stride"), py::arg("pad"),
+          py::arg("tr") = -1);
     m.def("conv2d_kloop_plan", &conv2d_kloop_plan,
           "'walk' or 'decode': the K loop conv2d_fwd[_stats] (mode 0) or "
           "conv2d_dgrad (mode 1) would run for this shape; kwalk -1 "

@@ -19,7 +19,8 @@ from . import functional as F_ops
 
 class Conv2d(nn.Conv2d):
     def forward(self, x):
-        return F_ops.conv2d(x, self.weight, self.bias, self.stride, self.padding)
+        return F_ops.conv2d(x, self.weight, self.bias, self.stride,
+                            self.padding, self.groups, self.dilation)
 
 
 class Linear(nn.Linear):

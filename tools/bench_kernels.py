@@ -9,6 +9,7 @@ Usage (on a GPU box):  python tools/bench_kernels.py [--resnet]
                        python tools/bench_kernels.py --kwalk
                        python tools/bench_kernels.py --stem
                        python tools/bench_kernels.py --linear
+                       python tools/bench_kernels.py --dwconv [--trs 4,8,32]
 
 Times conv fwd/dgrad/wgrad per shape with HIP events (200 reps after 20
 warmup) and prints achieved TFLOP/s next to microseconds, so kernel A/B
@@ -626,8 +627,95 @@ def bench_stem(rounds):
     _wide_slab_rows(ext, rounds)
 
 
+# the nine distinct MobileNetV1 depthwise shapes (C, H = W, stride), pad 1
+DWCONV = [(32, 112, 1), (64, 112, 2), (128, 56, 1), (128, 56, 2),
+          (256, 28, 1), (256, 28, 2), (512, 14, 1), (512, 14, 2),
+          (1024, 7, 1)]
+HBM_PEAK = 8.0e12      # bytes/s, MI355X HBM3E
+
+
+def bench_dwconv(rounds, trs):
+    """Depthwise 3x3 kernels (dwconv.hip) at B = 256 on MobileNetV1's shapes
+    against torch's own kernels for F.conv2d(groups=C) in bf16 channels_last
+    (aten convolution / convolution_backward with one output mask bit each),
+    alternated in one process.  Each row: median us of our kernel (min-max),
+    GB/s on the minimum bytes the op must move (every operand read once,
+    every result written once; the fp32 slabs not counted), that minimum over
+    the 8 TB/s HBM peak as a share of the measured time, torch's median and
+    torch / ours.  Outputs are compared with torch's before timing.  `trs`:
+    further strip heights timed for the forward (the plan's choice is -1)."""
+    ext = load_extension(required=True)
+    dev = torch.device("cuda:0")
+    N, pad = 256, 1
+    aten = torch.ops.aten
+    print(f"{'C':>5s} {'H':>4s} {'s':>2s} {'op':10s} {'med us':>8s} "
+          f"{'min':>8s} {'max':>8s} {'GB/s':>7s} {'%HBM':>6s} "
+          f"{'torch us':>9s} {'torch/ours':>10s}")
+    for C, H, stride in DWCONV:
+        g = torch.Generator(device=dev).manual_seed(C + H + stride)
+        P = (H + 2 * pad - 3) // stride + 1
+        x = torch.randn(N, C, H, H, device=dev, generator=g) \
+            .to(torch.bfloat16).contiguous(memory_format=CL)
+        dy = torch.randn(N, C, P, P, device=dev, generator=g) \
+            .to(torch.bfloat16).contiguous(memory_format=CL)
+        w = torch.randn(C, 1, 3, 3, device=dev, generator=g) / 3.0
+        wb = w.to(torch.bfloat16).contiguous(memory_format=CL)
+        xb, yb = x.numel() * 2, dy.numel() * 2
+
+        def t_bwd(mask):
+            return aten.convolution_backward(
+                dy, x, wb, None, [stride] * 2, [pad] * 2, [1, 1], False,
+                [0, 0], C, mask)
+        ops = {
+            "fwd": (lambda tr=-1: ext.dwconv2d_fwd(x, w, None, stride, pad,
+                                                   False, tr)[0],
+                    lambda: torch.nn.functional.conv2d(
+                        x, wb, None, stride, pad, 1, C), xb + yb),
+            "fwd+stats": (lambda: ext.dwconv2d_fwd(x, w, None, stride, pad,
+                                                   True)[0],
+                          None, xb + yb),
+            "dgrad": (lambda: ext.dwconv2d_dgrad(dy, w, H, H, stride, pad),
+                      lambda: t_bwd([True, False, False])[0], xb + yb),
+            "wgrad": (lambda: ext.dwconv2d_wgrad(dy, x, stride, pad,
+                                                 False)[0],
+                      lambda: t_bwd([False, True, False])[1].float(),
+                      xb + yb),
+        }
+        for name, (ours, theirs, nbytes) in ops.items():
+            variants = {"ours": ours}
+            if theirs is not None:
+                a, b = ours().float(), theirs().float()
+                err = float((a - b).abs().max() / b.abs().max())
+                # torch's results are bf16 (its wgrad too): one bf16 ulp of
+                # the largest element is 2^-7 of it
+                if err > 2.0 ** -5:
+                    raise RuntimeError(f"dwconv {name} C{C} H{H} s{stride}: "
+                                       f"differs from torch by {err:.3g}")
+                variants["torch"] = theirs
+            if name == "fwd":
+                for tr in trs:
+                    variants[f"tr{tr}"] = (lambda tr=tr: ours(tr))
+            res = _time_alternating(variants, rounds=rounds, warmup=10)
+            med, lo, hi = res["ours"]
+            tm = res["torch"][0] if "torch" in res else float("nan")
+            print(f"{C:5d} {H:4d} {stride:2d} {name:10s} {med:8.1f} {lo:8.1f} "
+                  f"{hi:8.1f} {nbytes / med / 1e3:7.0f} "
+                  f"{nbytes / HBM_PEAK * 1e6 / med * 100:6.1f} {tm:9.1f} "
+                  f"{tm / med:10.2f}", flush=True)
+            for tr in (trs if name == "fwd" else ()):
+                m2 = res[f"tr{tr}"]
+                print(f"{'':12s} fwd tr={tr:<3d} {m2[0]:8.1f} {m2[1]:8.1f} "
+                      f"{m2[2]:8.1f}", flush=True)
+        del x, dy
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--dwconv", action="store_true")
+    ap.add_argument("--trs", default="",
+                    help="further forward strip heights for --dwconv, comma "
+                         "separated (e.g. 4,8,32)")
     ap.add_argument("--clip", action="store_true")
     ap.add_argument("--wgradbias", action="store_true")
     ap.add_argument("--wgraddma", action="store_true")
@@ -649,6 +737,10 @@ def main():
     ap.add_argument("--bnpool", action="store_true")
     ap.add_argument("--reps", type=int, default=200)
     args = ap.parse_args()
+    if args.dwconv:
+        bench_dwconv(rounds=30,
+                     trs=[int(v) for v in args.trs.split(",") if v])
+        return
     if args.clip:
         bench_clip(rounds=30)
         return
