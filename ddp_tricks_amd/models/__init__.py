@@ -1,5 +1,7 @@
 from .mobilenet import mobilenet_v1  # noqa: F401
-from .resnet import resnet18, resnet34, resnet50  # noqa: F401
+from .resnet import (  # noqa: F401
+    resnet18, resnet34, resnet50, resnext50_32x4d, resnext101_32x8d,
+)
 from .toy_net import Toy_Net  # noqa: F401
 from .vgg import vgg16_bn  # noqa: F401
 
@@ -8,6 +10,8 @@ _REGISTRY = {
     "resnet18": resnet18,
     "resnet34": resnet34,
     "resnet50": resnet50,
+    "resnext50_32x4d": resnext50_32x4d,
+    "resnext101_32x8d": resnext101_32x8d,
     "vgg16": vgg16_bn,
     "mobilenet_v1": mobilenet_v1,
 }

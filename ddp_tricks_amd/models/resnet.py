@@ -1,5 +1,5 @@
-"""ResNet-18/34/50 on the framework's HIP-backed modules (BASELINE.json
-configs 4-5).
+"""ResNet-18/34/50 and ResNeXt-50/101 on the framework's HIP-backed modules
+(BASELINE.json configs 4-5).
 
 MI355X-first block design: every BN+ReLU pair runs as one fused HIP kernel,
 and each block's closing ``relu(bn(out) + identity)`` is a single kernel via
@@ -13,6 +13,10 @@ interchangeable with stock definitions of the same architecture.
 
 ``cifar_stem=True`` (ResNet-18 CIFAR-10 config) replaces the 7x7/2 stem +
 3x3/2 maxpool with a 3x3/1 conv, the standard CIFAR variant.
+
+ResNeXt is the same Bottleneck with a grouped 3x3 (``groups``,
+``base_width``; torchvision's width rule), served by the grouped MFMA kernels
+(ops/hip/gconv.hip).
 """
 from __future__ import annotations
 
@@ -25,8 +29,9 @@ from ..ops.modules import (
 )
 
 
-def conv3x3(cin, cout, stride=1):
-    return Conv2d(cin, cout, 3, stride=stride, padding=1, bias=False)
+def conv3x3(cin, cout, stride=1, groups=1):
+    return Conv2d(cin, cout, 3, stride=stride, padding=1, bias=False,
+                  groups=groups)
 
 
 def conv1x1(cin, cout, stride=1):
@@ -55,13 +60,15 @@ class BasicBlock(nn.Module):
 class Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1,
+                 base_width=64):
         super().__init__()
-        self.conv1 = conv1x1(inplanes, planes)
-        self.bn1 = BatchNorm2d(planes, fuse_relu=True)
-        self.conv2 = conv3x3(planes, planes, stride)
-        self.bn2 = BatchNorm2d(planes, fuse_relu=True)
-        self.conv3 = conv1x1(planes, planes * self.expansion)
+        width = int(planes * base_width / 64) * groups
+        self.conv1 = conv1x1(inplanes, width)
+        self.bn1 = BatchNorm2d(width, fuse_relu=True)
+        self.conv2 = conv3x3(width, width, stride, groups)
+        self.bn2 = BatchNorm2d(width, fuse_relu=True)
+        self.conv3 = conv1x1(width, planes * self.expansion)
         self.bn3 = BatchNorm2d(planes * self.expansion, fuse_relu=True)
         self.relu = Identity()
         self.downsample = downsample
@@ -75,9 +82,13 @@ class Bottleneck(nn.Module):
 
 
 class ResNet(nn.Module):
-    def __init__(self, block, layers, num_classes=1000, cifar_stem=False):
+    def __init__(self, block, layers, num_classes=1000, cifar_stem=False,
+                 groups=1, width_per_group=64):
         super().__init__()
         self.inplanes = 64
+        # only Bottleneck takes them; the defaults build the plain ResNets
+        self.block_kw = ({} if (groups, width_per_group) == (1, 64) else
+                         dict(groups=groups, base_width=width_per_group))
         if cifar_stem:
             self.conv1 = Conv2d(3, 64, 3, stride=1, padding=1, bias=False)
             self.maxpool = Identity()
@@ -111,7 +122,8 @@ class ResNet(nn.Module):
         strides = [stride] + [1] * (blocks - 1)
         mods = []
         for s in strides:
-            mods.append(block(self.inplanes, planes, s, downsample))
+            mods.append(block(self.inplanes, planes, s, downsample,
+                              **self.block_kw))
             downsample = None
             self.inplanes = planes * block.expansion
         return nn.Sequential(*mods)
@@ -133,3 +145,13 @@ def resnet34(num_classes=1000, cifar_stem=False):
 
 def resnet50(num_classes=1000, cifar_stem=False):
     return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, cifar_stem)
+
+
+def resnext50_32x4d(num_classes=1000, cifar_stem=False):
+    return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, cifar_stem,
+                  groups=32, width_per_group=4)
+
+
+def resnext101_32x8d(num_classes=1000, cifar_stem=False):
+    return ResNet(Bottleneck, [3, 4, 23, 3], num_classes, cifar_stem,
+                  groups=32, width_per_group=8)

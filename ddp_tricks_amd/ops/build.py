@@ -29,6 +29,7 @@ SOURCES = [
     "gemm.hip",
     "conv.hip",
     "dwconv.hip",
+    "gconv.hip",
     "data.hip",
 ]
 

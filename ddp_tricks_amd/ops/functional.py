@@ -39,6 +39,9 @@ def weight_variant(w: torch.Tensor, variant: str) -> torch.Tensor:
               "nhwc_p8"  — bf16 channels_last with Cin zero-padded to 8
                            (MFMA path for C<8 stems, e.g. ResNet RGB)
               "wt2_p8"   — dgrad operand of the padded weights
+              "gconv"    — grouped 3x3 forward image, bf16 [C/64, 9, 64, 64]
+                           (block-diagonal 64x64 per span and tap)
+              "gconv_t"  — its dgrad image (taps flipped, blocks transposed)
 
     An entry is valid while ``w._version`` is unchanged, so every in-place
     write to the parameter itself (``w.mul_()``, ``w.copy_()``,
@@ -64,6 +67,11 @@ def weight_variant(w: torch.Tensor, variant: str) -> torch.Tensor:
                                              True)
             ent["nhwc" + sfx] = nhwc
             ent["wt2" + sfx] = wt2
+            return ent[variant]
+        if ext is not None and variant in ("gconv", "gconv_t"):
+            # one launch fills both grouped operand images; GPU only
+            ent["gconv"], ent["gconv_t"] = ext.gconv2d_pack(
+                w.detach().contiguous())
             return ent[variant]
         wb = w.detach().to(torch.bfloat16)
         if variant == "flat":
@@ -439,6 +447,84 @@ class _HIPDWConv2dStats(torch.autograd.Function):
         return dx, dw, db, None, None
 
 
+# --------------------------------------------------------- grouped conv2d ---
+
+G_SCOPE = ("groups > 1 with C_in == C_out == C, C % 64 == 0 and C / groups in "
+           "{4, 8, 16, 32, 64}, a 3x3 kernel, dilation 1, one stride of 1 or "
+           "2 and one padding of 0 or 1 for both dims and an fp32 weight")
+_G_CG = (4, 8, 16, 32, 64)
+
+
+def _g_in_scope(x, weight, stride, padding, groups, dilation) -> bool:
+    """Whether the grouped MFMA kernels (hip/gconv.hip) serve this conv."""
+    C = x.shape[1]
+    return (groups > 1 and dilation == 1 and C % 64 == 0 and C % groups == 0
+            and C // groups in _G_CG
+            and tuple(weight.shape) == (C, C // groups, 3, 3)
+            and weight.dtype == torch.float32
+            and stride in (1, 2) and padding in (0, 1))
+
+
+def _g_fwd(ctx, x, weight, bias, stride, padding, groups, want_stats):
+    ext = require_ext_for(x)
+    xb = _chlast(_to_bf16(x))
+    y, stats = ext.gconv2d_fwd(
+        xb, weight_variant(weight, "gconv"),
+        bias if bias is None else bias.detach().float().contiguous(),
+        groups, stride, padding, want_stats)
+    ctx.save_for_backward(xb, weight)
+    ctx.meta = (stride, padding, groups, x.dtype, bias is not None)
+    return y, stats
+
+
+def _g_bwd(ctx, dy):
+    xb, weight = ctx.saved_tensors
+    stride, padding, groups, x_dtype, has_bias = ctx.meta
+    ext = require_ext_for(dy)
+    dyb = _chlast(_to_bf16(dy))
+    dx = dw = db = None
+    if ctx.needs_input_grad[0]:
+        dx = ext.gconv2d_dgrad(dyb, weight_variant(weight, "gconv_t"),
+                               xb.shape[2], xb.shape[3], groups, stride,
+                               padding)
+        if x_dtype == torch.float32:
+            dx = dx.float()
+    if ctx.needs_input_grad[1]:
+        dw = ext.gconv2d_wgrad(dyb, xb, groups, stride, padding)
+    if has_bias and ctx.needs_input_grad[2]:
+        db = ext.col_sum(_nhwc_2d(dyb))
+    return dx, dw, db
+
+
+class _HIPGConv2d(torch.autograd.Function):
+    """Grouped 3x3 conv on the MFMA span kernels (see _g_in_scope)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, padding, groups):
+        return _g_fwd(ctx, x, weight, bias, stride, padding, groups, False)[0]
+
+    @staticmethod
+    def backward(ctx, dy):
+        dx, dw, db = _g_bwd(ctx, dy)
+        return dx, dw, db, None, None, None
+
+
+class _HIPGConv2dStats(torch.autograd.Function):
+    """_HIPGConv2d that also emits the consuming BN's partial statistics
+    (non-differentiable), like _HIPConv2dStats."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, padding, groups):
+        y, stats = _g_fwd(ctx, x, weight, bias, stride, padding, groups, True)
+        ctx.mark_non_differentiable(stats)
+        return y, stats
+
+    @staticmethod
+    def backward(ctx, dy, dstats):
+        dx, dw, db = _g_bwd(ctx, dy)
+        return dx, dw, db, None, None, None
+
+
 def conv2d(x, weight, bias=None, stride=1, padding=0, groups=1, dilation=1):
     if x.is_cuda and require_ext_for(x) is not None:
         stride = _uniform(stride, "stride")
@@ -447,12 +533,15 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, groups=1, dilation=1):
         if groups != 1 or dilation != 1:
             if _dw_in_scope(x, weight, stride, padding, groups, dilation):
                 return _HIPDWConv2d.apply(x, weight, bias, stride, padding)
+            if _g_in_scope(x, weight, stride, padding, groups, dilation):
+                return _HIPGConv2d.apply(x, weight, bias, stride, padding,
+                                         groups)
             raise ValueError(
                 f"HIP conv2d: groups={groups}, dilation={dilation} with "
                 f"weight {tuple(weight.shape)}, stride={stride}, "
                 f"padding={padding} is not supported; besides dense convs "
                 f"(groups=1, dilation=1) the kernels serve depthwise convs: "
-                f"{DW_SCOPE}")
+                f"{DW_SCOPE}; and grouped convs: {G_SCOPE}")
         # NOTE: a 1x1-as-GEMM route through the linear kernels was tried and
         # REVERTED — measured 2.6 ms vs 0.27 ms for the conv path at
         # ResNet-50's [M~800k, 64x64] shapes (the GEMM ladder's split-K is
@@ -1444,19 +1533,25 @@ def conv_bn(conv_mod, bn_mod, x, residual=None, pool=None):
                                                  (1, 1)) in ((1, 1), 1))
     stats = None
     groups = getattr(conv_mod, "groups", 1)
+    grouped = False
     if use_stats and groups != 1:
-        # a depthwise conv in the direct kernels' scope emits the slab too;
-        # any other grouped conv goes through conv_mod and is refused there
-        use_stats = _dw_in_scope(x, conv_mod.weight,
-                                 _uniform(conv_mod.stride, "stride"),
-                                 _uniform(conv_mod.padding, "padding"),
-                                 groups, 1)
+        # a depthwise or grouped conv in its kernels' scope emits the slab
+        # too; any other goes through conv_mod and is refused there
+        scope = (x, conv_mod.weight, _uniform(conv_mod.stride, "stride"),
+                 _uniform(conv_mod.padding, "padding"), groups, 1)
+        grouped = not _dw_in_scope(*scope) and _g_in_scope(*scope)
+        use_stats = grouped or _dw_in_scope(*scope)
     if use_stats:
         stride = _uniform(conv_mod.stride, "stride")
         padding = _uniform(conv_mod.padding, "padding")
-        fn = _HIPConv2dStats if groups == 1 else _HIPDWConv2dStats
-        y, stats = fn.apply(x, conv_mod.weight, conv_mod.bias, stride,
-                            padding)
+        if grouped:
+            y, stats = _HIPGConv2dStats.apply(x, conv_mod.weight,
+                                              conv_mod.bias, stride, padding,
+                                              groups)
+        else:
+            fn = _HIPConv2dStats if groups == 1 else _HIPDWConv2dStats
+            y, stats = fn.apply(x, conv_mod.weight, conv_mod.bias, stride,
+                                padding)
     else:
         y = conv_mod(x)
     if (pool is not None and residual is None

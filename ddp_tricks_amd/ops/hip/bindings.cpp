@@ -185,6 +185,19 @@ std::tuple<long, long, long, long> dwconv2d_plan(std::string op, long N,
                                                  long stride, long pad,
                                                  long tr);
 
+// gconv.hip
+std::tuple<at::Tensor, at::Tensor> gconv2d_pack(at::Tensor w);
+std::tuple<at::Tensor, at::Tensor> gconv2d_fwd(
+    at::Tensor x, at::Tensor wimg, c10::optional<at::Tensor> bias, long groups,
+    long stride, long pad, bool want_stats);
+at::Tensor gconv2d_dgrad(at::Tensor dy, at::Tensor wimg_t, long H, long W,
+                         long groups, long stride, long pad);
+at::Tensor gconv2d_wgrad(at::Tensor dy, at::Tensor x, long groups, long stride,
+                         long pad);
+std::tuple<std::string, long, long, long, long, long> gconv2d_plan(
+    std::string op, long N, long C, long H, long W, long groups, long stride,
+    long pad);
+
 // data.hip
 std::vector<at::Tensor> batch_gather_aug(at::Tensor store, at::Tensor labels,
                                          at::Tensor index, at::Tensor lut,
@@ -417,6 +430,32 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("op"), py::arg("N"), py::arg("C"), py::arg("H"),
           py::arg("W"), py::arg("stride"), py::arg("pad"),
           py::arg("tr") = -1);
+    m.def("gconv2d_pack", &gconv2d_pack,
+          "grouped 3x3 weight pack: fp32 master [C,Cg,3,3] -> (forward image, "
+          "dgrad image), each bf16 [C/64, 9, 64, 64]",
+          py::arg("w"));
+    m.def("gconv2d_fwd", &gconv2d_fwd,
+          "grouped 3x3 forward from bf16 channels_last x and the forward "
+          "image: (y, slab); slab is the [2, C, row tiles] BN partial slab "
+          "with want_stats, else undefined",
+          py::arg("x"), py::arg("wimg"), py::arg("bias") = c10::nullopt,
+          py::arg("groups") = 1, py::arg("stride") = 1, py::arg("pad") = 0,
+          py::arg("want_stats") = false);
+    m.def("gconv2d_dgrad", &gconv2d_dgrad,
+          "grouped 3x3 backward-data from dy and the dgrad image: dx bf16 "
+          "[N,C,H,W], every element written",
+          py::arg("dy"), py::arg("wimg_t"), py::arg("H"), py::arg("W"),
+          py::arg("groups"), py::arg("stride") = 1, py::arg("pad") = 0);
+    m.def("gconv2d_wgrad", &gconv2d_wgrad,
+          "grouped 3x3 backward-weight: dw fp32 [C,Cg,3,3]",
+          py::arg("dy"), py::arg("x"), py::arg("groups"),
+          py::arg("stride") = 1, py::arg("pad") = 0);
+    m.def("gconv2d_plan", &gconv2d_plan,
+          "(instantiation, row tile, grid x, grid y, grid z, split) of the "
+          "grouped kernel for op 'fwd', 'dgrad' or 'wgrad' over an [N,C,H,W] "
+          "input; launches nothing",
+          py::arg("op"), py::arg("N"), py::arg("C"), py::arg("H"),
+          py::arg("W"), py::arg("groups"), py::arg("stride"), py::arg("pad"));
     m.def("conv2d_kloop_plan", &conv2d_kloop_plan,
           "'walk' or 'decode': the K loop conv2d_fwd[_stats] (mode 0) or "
           "conv2d_dgrad (mode 1) would run for this shape; kwalk -1 "

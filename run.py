@@ -41,7 +41,8 @@ def parse_args():
     # extensions beyond the reference's 10-flag contract
     parser.add_argument("--model", default="toy_net", type=str,
                         help="model registry name (toy_net, vgg16, resnet18, "
-                             "resnet34, resnet50, mobilenet_v1)")
+                             "resnet34, resnet50, resnext50_32x4d, "
+                             "resnext101_32x8d, mobilenet_v1)")
     parser.add_argument("--dataset", default="mnist", type=str,
                         help="dataset registry name (mnist, cifar10, "
                              "imagenet_synthetic)")

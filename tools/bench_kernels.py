@@ -10,6 +10,7 @@ Usage (on a GPU box):  python tools/bench_kernels.py [--resnet]
                        python tools/bench_kernels.py --stem
                        python tools/bench_kernels.py --linear
                        python tools/bench_kernels.py --dwconv [--trs 4,8,32]
+                       python tools/bench_kernels.py --gconv
 
 Times conv fwd/dgrad/wgrad per shape with HIP events (200 reps after 20
 warmup) and prints achieved TFLOP/s next to microseconds, so kernel A/B
@@ -710,8 +711,96 @@ def bench_dwconv(rounds, trs):
         torch.cuda.empty_cache()
 
 
+# ResNeXt-50 32x4d's grouped convs (C, H, stride, Cg) and a Cg = 64 layer
+GCONV = [(128, 56, 1, 4), (256, 56, 2, 8), (256, 28, 1, 8), (512, 28, 2, 16),
+         (512, 14, 1, 16), (1024, 14, 2, 32), (1024, 7, 1, 32),
+         (2048, 7, 1, 64)]
+
+
+def bench_gconv(rounds):
+    """Grouped 3x3 kernels (gconv.hip) at B = 256, pad 1, against (a) torch's
+    own kernels for F.conv2d(groups=) / convolution_backward in bf16
+    channels_last and (b), forward only, this project's dense path on the
+    block-diagonally expanded weight; alternated in one process, 30 warm-up
+    calls, device events around 10 calls.  Each row: median us (min-max), the
+    share of the HBM-bound time (the two activation tensors the op must move,
+    once each, at 8 TB/s: x and y forward, dy and dx dgrad, dy and x wgrad),
+    the comparisons' medians and their ratio to ours.  Outputs are compared
+    with torch's before timing."""
+    ext = load_extension(required=True)
+    dev = torch.device("cuda:0")
+    N, pad = 256, 1
+    aten = torch.ops.aten
+    print(f"{'C':>5s} {'H':>4s} {'s':>2s} {'Cg':>3s} {'op':6s} {'med us':>8s} "
+          f"{'min':>8s} {'max':>8s} {'%HBM':>6s} {'bound':>6s} "
+          f"{'torch us':>9s} {'torch/ours':>10s} {'dense us':>9s} "
+          f"{'dense/ours':>10s}")
+    for C, H, stride, Cg in GCONV:
+        groups = C // Cg
+        g = torch.Generator(device=dev).manual_seed(C + H + stride)
+        P = (H + 2 * pad - 3) // stride + 1
+        x = torch.randn(N, C, H, H, device=dev, generator=g) \
+            .to(torch.bfloat16).contiguous(memory_format=CL)
+        dy = torch.randn(N, C, P, P, device=dev, generator=g) \
+            .to(torch.bfloat16).contiguous(memory_format=CL)
+        w = torch.randn(C, Cg, 3, 3, device=dev, generator=g) / 3.0
+        wb = w.to(torch.bfloat16).contiguous(memory_format=CL)
+        img, img_t = ext.gconv2d_pack(w)
+        wd = torch.zeros(C, C, 3, 3, device=dev)
+        for k in range(groups):
+            wd[k * Cg:(k + 1) * Cg, k * Cg:(k + 1) * Cg] = \
+                w[k * Cg:(k + 1) * Cg]
+        wdb = wd.to(torch.bfloat16).contiguous(memory_format=CL)
+        del wd
+        xb, yb = x.numel() * 2, dy.numel() * 2
+
+        def t_bwd(mask):
+            return aten.convolution_backward(
+                dy, x, wb, None, [stride] * 2, [pad] * 2, [1, 1], False,
+                [0, 0], groups, mask)
+        ops = {
+            "fwd": (lambda: ext.gconv2d_fwd(x, img, None, groups, stride, pad,
+                                            False)[0],
+                    lambda: torch.nn.functional.conv2d(
+                        x, wb, None, stride, pad, 1, groups),
+                    lambda: ext.conv2d_fwd(x, wdb, None, stride, pad),
+                    "x+y"),
+            "dgrad": (lambda: ext.gconv2d_dgrad(dy, img_t, H, H, groups,
+                                                stride, pad),
+                      lambda: t_bwd([True, False, False])[0], None, "dy+dx"),
+            "wgrad": (lambda: ext.gconv2d_wgrad(dy, x, groups, stride, pad),
+                      lambda: t_bwd([False, True, False])[1].float(), None,
+                      "dy+x"),
+        }
+        for name, (ours, theirs, dense, bound) in ops.items():
+            variants = {"ours": ours, "torch": theirs}
+            if dense is not None:
+                variants["dense"] = dense
+            a = ours().float()
+            for other in list(variants)[1:]:
+                b = variants[other]().float()
+                err = float((a - b).abs().max() / b.abs().max())
+                # torch's results are bf16 (its wgrad too): one bf16 ulp of
+                # the largest element is 2^-7 of it
+                if err > 2.0 ** -5:
+                    raise RuntimeError(f"gconv {name} C{C} H{H} s{stride}: "
+                                       f"differs from {other} by {err:.3g}")
+            res = _time_alternating(variants, rounds=rounds, warmup=30)
+            med, lo, hi = res["ours"]
+            tm = res["torch"][0]
+            dm = res["dense"][0] if dense is not None else float("nan")
+            print(f"{C:5d} {H:4d} {stride:2d} {Cg:3d} {name:6s} {med:8.1f} "
+                  f"{lo:8.1f} {hi:8.1f} "
+                  f"{(xb + yb) / HBM_PEAK * 1e6 / med * 100:6.1f} {bound:>6s} "
+                  f"{tm:9.1f} {tm / med:10.2f} {dm:9.1f} {dm / med:10.2f}",
+                  flush=True)
+        del x, dy
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--gconv", action="store_true")
     ap.add_argument("--dwconv", action="store_true")
     ap.add_argument("--trs", default="",
                     help="further forward strip heights for --dwconv, comma "
@@ -737,6 +826,9 @@ def main():
     ap.add_argument("--bnpool", action="store_true")
     ap.add_argument("--reps", type=int, default=200)
     args = ap.parse_args()
+    if args.gconv:
+        bench_gconv(rounds=30)
+        return
     if args.dwconv:
         bench_dwconv(rounds=30,
                      trs=[int(v) for v in args.trs.split(",") if v])
