@@ -163,10 +163,16 @@ std::vector<at::Tensor> conv2d_dgrad_bn(at::Tensor dy, at::Tensor wt2,
                                         at::Tensor bn_mean,
                                         at::Tensor bn_invstd);
 at::Tensor conv2d_wgrad(at::Tensor dy, at::Tensor x, long R, long S,
-                        long stride, long pad);
+                        long stride, long pad, long walk);
 std::vector<at::Tensor> conv2d_wgrad_bias(at::Tensor dy, at::Tensor x,
                                           long R, long S, long stride,
-                                          long pad);
+                                          long pad, long walk);
+std::tuple<std::string, long, long, long> conv2d_wgrad_kloop_plan(
+    long N, long C, long H, long W, long Ko, long R, long S, long stride,
+    long pad, bool want_bias, long walk);
+std::vector<std::tuple<long, long, long, bool>> conv2d_wgrad_walk_rows(
+    long N, long C, long H, long W, long Ko, long R, long S, long stride,
+    long pad, bool want_bias, long split, long chunk_row, long tiles);
 std::tuple<std::string, long, bool> conv2d_wgrad_plan(
     long N, long C, long H, long W, long Ko, long R, long S, long stride,
     long pad, bool want_bias);
@@ -472,8 +478,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("Ko"), py::arg("R"), py::arg("S"), py::arg("stride"),
           py::arg("pad"), py::arg("group") = -1);
     m.def("conv2d_dgrad_bn", &conv2d_dgrad_bn);
-    m.def("conv2d_wgrad", &conv2d_wgrad);
-    m.def("conv2d_wgrad_bias", &conv2d_wgrad_bias);
+    m.def("conv2d_wgrad", &conv2d_wgrad, py::arg("dy"), py::arg("x"),
+          py::arg("R"), py::arg("S"), py::arg("stride"), py::arg("pad"),
+          py::arg("walk") = -1);
+    m.def("conv2d_wgrad_bias", &conv2d_wgrad_bias, py::arg("dy"),
+          py::arg("x"), py::arg("R"), py::arg("S"), py::arg("stride"),
+          py::arg("pad"), py::arg("walk") = -1);
+    m.def("conv2d_wgrad_kloop_plan", &conv2d_wgrad_kloop_plan,
+          "('walk' or 'decode', dn, dp, dq): the tile loop conv2d_wgrad[_bias] "
+          "would run for this shape, and the tile step S*DEPTH = dn*P*Q + "
+          "dp*Q + dq of a wide_dma leaf (zeros otherwise); walk -1 automatic, "
+          "0 decode, 1 forces the carried rows; launches nothing",
+          py::arg("N"), py::arg("C"), py::arg("H"), py::arg("W"),
+          py::arg("Ko"), py::arg("R"), py::arg("S"), py::arg("stride"),
+          py::arg("pad"), py::arg("want_bias"), py::arg("walk") = -1);
+    m.def("conv2d_wgrad_walk_rows", &conv2d_wgrad_walk_rows,
+          "[(n, p, q, valid)] of the GEMM row split*DEPTH + chunk_row over "
+          "`tiles` steps of the carried-row state; launches nothing",
+          py::arg("N"), py::arg("C"), py::arg("H"), py::arg("W"),
+          py::arg("Ko"), py::arg("R"), py::arg("S"), py::arg("stride"),
+          py::arg("pad"), py::arg("want_bias"), py::arg("split"),
+          py::arg("chunk_row"), py::arg("tiles"));
     m.def("conv2d_wgrad_plan", &conv2d_wgrad_plan,
           "(leaf name, split, fused_bias) conv2d_wgrad[_bias] would run for "
           "this shape under this process's DDPX_WGRAD_V; launches nothing",

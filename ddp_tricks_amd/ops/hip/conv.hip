@@ -1262,6 +1262,35 @@ void k_conv_wgrad_wide_pair(const bf16* __restrict__ dy,
     }
 }
 
+// Carried rows of k_conv_wgrad_wide_walk.  A block's tiles lie m_step =
+// S*DEPTH GEMM rows apart, m_step = dn*P*Q + dp*Q + dq with dq < Q, dp < P
+// (host: make_wgrad_walk), so a lane's (n, p, q) moves by (dn, dp, dq) per
+// tile with at most one carry per level.  d0 is the x BYTE step of a tile
+// without carries, d1 / d2 what a carry of q into p / p into n adds to it;
+// ystep the dy byte step.
+struct WgradWalk {
+    int dn, dp, dq;
+    int d0, d1, d2, ystep;
+};
+
+// One tile step of a carried row.  ub = q*stride - Qs and vb = p*stride - Ps
+// as unsigned (Qs = Q*stride, Ps = P*stride), so "q + dq >= Q" is the carry
+// out of ub + dqs.  c1: q carried into p; c2: p carried into n.  ONE function
+// for the kernel's loop and the host's row list (conv2d_wgrad_walk_rows).
+__host__ __device__ inline void wgrad_walk_step(
+        unsigned& ub, unsigned& vb, unsigned dqs, unsigned Qs, unsigned dps,
+        unsigned st, unsigned Ps, bool& c1, bool& c2) {
+    // after a carry r is the new q*stride itself, below Qs, and r - Qs wraps
+    // to the new ub; without one r - Qs is merely smaller: max picks both
+    unsigned r = ub + dqs;
+    c1 = r < dqs;
+    ub = r > r - Qs ? r : r - Qs;
+    const unsigned a = dps + (c1 ? st : 0u);
+    r = vb + a;
+    c2 = r < a;
+    vb = r > r - Ps ? r : r - Ps;
+}
+
 // fd_div as a select, not a branch: keeps wide_dma's per-tile address block
 // one straight run of VALU the scheduler can place under the DMA wait
 DEV_INLINE unsigned fd_div_sel(unsigned n, FastDiv f) {
@@ -1475,6 +1504,233 @@ void k_conv_wgrad_wide_dma(const bf16* __restrict__ dy,
                 float s = join[tid];
                 #pragma unroll
                 for (int gi = 1; gi < 8; ++gi) s += join[gi * 128 + tid];
+                slab[(long)S * cs.Ko * Kgemm + (long)split * cs.Ko + row] = s;
+            }
+        }
+    }
+}
+
+// k_conv_wgrad_wide_dma with carried rows: same grid, slab, staging lanes,
+// swizzle, zero fills, tile order, MFMA order, bias sum and epilogue, so dw
+// and db are bit-identical; only the per-tile row decode of sources() is
+// gone.  Per chunk the lane's row (n, p, q) lives as ub = q*stride - Q*stride
+// and vb = p*stride - P*stride (mod 2^32, so a carry is the adder's carry out:
+// wgrad_walk_step) and as ox, the BYTE distance of its x segment from
+// g_zero16; oy is that distance for the dy segment of chunk 0, chunk i lies
+// i*y16 behind it.  All of it is integers: an address is formed, and cast,
+// only for the row a tile really reads, and "read zeros instead" is the
+// distance 0.  Lanes whose column is constant padding (ko >= Ko, rsc >=
+// Kgemm) carry distance 0 and zero steps, so they need no per-tile select.
+// The tile loop holds no multiply and no division.  PAD = false (pad 0) is
+// the loop without the h / w tests, an instantiation of its own because the
+// two loops in one kernel spilled; rows past M exist only in a block's last
+// tile, behind a uniform branch.
+template <int DEPTH = 64, bool BIAS = false, bool PAD = true>
+__global__ __launch_bounds__(256, 3)
+void k_conv_wgrad_wide_walk(const bf16* __restrict__ dy,
+                            const bf16* __restrict__ x,
+                            float* __restrict__ slab, ConvShape cs, long M,
+                            int Kgemm, int S, WgradWalk wk) {
+    __shared__ __align__(16) bf16 img_a[DEPTH][128];   // [m][ko]
+    __shared__ __align__(16) bf16 img_b[DEPTH][128];   // [m][rsc]
+    constexpr int NCH = DEPTH / 16;   // 4-row glds chunks per wave per image
+    const int ko0 = blockIdx.x * 128;
+    const int rc0 = blockIdx.y * 128;
+    const int split = blockIdx.z;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wid = tid >> 6, wr = wid >> 1, wc = wid & 1;
+    // the wave index as a scalar, so the DMA's LDS base is one too
+    const int widu = __builtin_amdgcn_readfirstlane(wid);
+
+    // ---- staging: wave wid fills chunks wid + 4i, rows 4*chunk + srow ----
+    const int srow = lane >> 4;
+    const int lseg = (lane & 15) ^ (2 * (srow | (((wid >> 1) & 1) << 2)));
+    const int a_ko = ko0 + lseg * 8;
+    const bool a_ok = a_ko < cs.Ko;
+    const int b_gk = rc0 + lseg * 8;
+    const bool b_ok = b_gk < Kgemm;
+    int b_c = 0, b_dh = 0, b_dw = 0;
+    if (b_ok) {
+        unsigned rs = fd_div(b_gk, cs.fdC);
+        b_c = fd_mod(b_gk, cs.fdC, rs);
+        unsigned r = fd_div(rs, cs.fdS);
+        b_dw = (int)fd_mod(rs, cs.fdS, r) - cs.pad;
+        b_dh = (int)r - cs.pad;
+    }
+    const long zaddr = (long)g_zero16;
+    const long m_begin = (long)split * DEPTH;
+    const long m_step = (long)S * DEPTH;
+    const unsigned st = cs.stride, Qs = cs.Q * st, Ps = cs.P * st;
+    const unsigned dqs = wk.dq * st, dps = wk.dp * st;
+    unsigned ub[NCH], vb[NCH];
+    long ox[NCH], oy = 0;
+    #pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+        // the block's first tile: today's FastDiv decode, once
+        const unsigned gm = (unsigned)m_begin + (wid + 4 * i) * 4 + srow;
+        unsigned rem = fd_div_sel(gm, cs.fdQ);
+        unsigned q = fd_mod(gm, cs.fdQ, rem);
+        unsigned n = fd_div_sel(rem, cs.fdP);
+        unsigned p = fd_mod(rem, cs.fdP, n);
+        ub[i] = q * st - Qs;
+        vb[i] = p * st - Ps;
+        const long h = (long)(p * st) + b_dh, wcol = (long)(q * st) + b_dw;
+        ox[i] = b_ok ? (long)x - zaddr +
+                       2 * ((((long)n * cs.H + h) * cs.W + wcol) * cs.C + b_c)
+                     : 0;
+        if (i == 0)
+            oy = a_ok ? (long)dy - zaddr + 2 * ((long)gm * cs.Ko + a_ko) : 0;
+    }
+    const int l_d0 = b_ok ? wk.d0 : 0;
+    const int l_d1 = b_ok ? wk.d0 + wk.d1 : 0;
+    const int l_d2 = b_ok ? wk.d2 : 0;
+    const int l_ys = a_ok ? wk.ystep : 0;
+    const long y16 = a_ok ? 2 * 16 * cs.Ko : 0;
+    // ub + kw = q*stride + b_dw, the x column; vb + kh the x row
+    const unsigned kw = Qs + b_dw, kh = Ps + b_dh;
+
+    // ---- fragment reads: element offsets, constant over tiles ----
+    const int g = lane & 15;
+    const int rsw = 2 * ((g >> 2) | (((lane >> 4) & 1) << 2));
+    const int rbase = ((lane >> 4) * 8 + (g >> 2)) * 128 + (g & 1) * 4;
+    const int rseg = (g & 3) >> 1;
+    int offa[4], offb[4];
+    #pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        offa[i] = rbase + ((wr * 8 + i * 2 + rseg) ^ rsw) * 8;
+        offb[i] = rbase + ((wc * 8 + i * 2 + rseg) ^ rsw) * 8;
+    }
+    auto frag = [](const bf16* p) {
+        tr16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+            (lds_tr16_ptr)p);
+        tr16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+            (lds_tr16_ptr)(p + 4 * 128));
+        return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+    };
+
+    f32x4 acc[4][4] = {};
+    [[maybe_unused]] float bsum[4] = {};
+
+    for (long mt = m_begin; mt < M; mt += m_step) {
+        long pa[NCH], pb[NCH];   // distances from g_zero16
+        #pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            pa[i] = oy + i * y16;
+            pb[i] = ox[i];
+            if constexpr (PAD) {
+                const bool in = (ub[i] + kw < (unsigned)cs.W) &
+                                (vb[i] + kh < (unsigned)cs.H);
+                pb[i] = in ? pb[i] : 0;
+            }
+        }
+        if (mt + DEPTH > M) {
+            // keeps this a branch: the selects stay out of the full tiles
+            asm volatile("");
+            const int left = (int)(M - mt) - (wid * 4 + srow);
+            #pragma unroll
+            for (int i = 0; i < NCH; ++i) {
+                const bool m_ok = 16 * i < left;
+                pa[i] = m_ok ? pa[i] : 0;
+                pb[i] = m_ok ? pb[i] : 0;
+            }
+        }
+        #pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            __builtin_amdgcn_global_load_lds(
+                (const __attribute__((address_space(1))) unsigned short*)
+                    (zaddr + pa[i]),
+                (__attribute__((address_space(3))) unsigned short*)
+                    &img_a[(widu + 4 * i) * 4][0], 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(
+                (const __attribute__((address_space(1))) unsigned short*)
+                    (zaddr + pb[i]),
+                (__attribute__((address_space(3))) unsigned short*)
+                    &img_b[(widu + 4 * i) * 4][0], 16, 0, 0);
+        }
+        // step the rows while this tile's DMA is in flight
+        #pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            bool c1, c2;
+            wgrad_walk_step(ub[i], vb[i], dqs, Qs, dps, st, Ps, c1, c2);
+            ox[i] += (c1 ? l_d1 : l_d0) + (c2 ? l_d2 : 0);
+        }
+        oy += l_ys;
+        __syncthreads();   // vmcnt(0) for the in-flight glds + barrier
+
+        if constexpr (BIAS) {
+            if (blockIdx.y == 0) {
+                // as k_conv_wgrad_wide_dma, the four adds kept apart (no
+                // packed fp32 add: the empty asm hides them from the
+                // vectorizer; same order, same bits)
+                const int kq = tid & 31;
+                const bf16* rp = &img_a[(tid >> 5) * (DEPTH / 8)][(kq & 1) * 4];
+                #pragma unroll
+                for (int i = 0; i < DEPTH / 8; ++i) {
+                    const int row = (tid >> 5) * (DEPTH / 8) + i;
+                    const int sw = 2 * ((row & 3) | (((row >> 3) & 1) << 2));
+                    s16x4 v = *reinterpret_cast<const s16x4*>(
+                        rp + i * 128 + (((kq >> 1) ^ sw) << 3));
+                    #pragma unroll
+                    for (int jj = 0; jj < 4; ++jj) {
+                        bsum[jj] += us2f((unsigned short)v[jj]);
+                        asm("" : "+v"(bsum[jj]));
+                    }
+                }
+            }
+        }
+
+        #pragma unroll
+        for (int ks = 0; ks < DEPTH; ks += 32) {
+            bf16x8_t af[4], bfr[4];
+            #pragma unroll
+            for (int mi = 0; mi < 4; ++mi)
+                af[mi] = frag(&img_a[ks][0] + offa[mi]);
+            #pragma unroll
+            for (int ni = 0; ni < 4; ++ni)
+                bfr[ni] = frag(&img_b[ks][0] + offb[ni]);
+            #pragma unroll
+            for (int mi = 0; mi < 4; ++mi)
+                #pragma unroll
+                for (int ni = 0; ni < 4; ++ni)
+                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        af[mi], bfr[ni], acc[mi][ni], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+
+    // the epilogue's thread coordinates, derived afresh behind the loop so
+    // that none of them holds a register across it
+    int te = tid;
+    asm volatile("" : "+v"(te));
+    const int le = te & 63, wre = te >> 7, wce = (te >> 6) & 1;
+    #pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+        #pragma unroll
+        for (int ni = 0; ni < 4; ++ni) {
+            int col = rc0 + wce * 64 + ni * 16 + (le & 15);
+            if (col >= Kgemm) continue;
+            #pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                int row = ko0 + wre * 64 + mi * 16 + (le >> 4) * 4 + r;
+                if (row >= cs.Ko) continue;
+                slab[((long)split * cs.Ko + row) * Kgemm + col] =
+                    acc[mi][ni][r];
+            }
+        }
+
+    if constexpr (BIAS) {
+        if (blockIdx.y == 0) {
+            float* join = reinterpret_cast<float*>(&img_a[0][0]);  // [8][128]
+            #pragma unroll
+            for (int jj = 0; jj < 4; ++jj)
+                join[(te >> 5) * 128 + (te & 31) * 4 + jj] = bsum[jj];
+            __syncthreads();
+            const int row = ko0 + te;
+            if (te < 128 && row < cs.Ko) {
+                float s = join[te];
+                #pragma unroll
+                for (int gi = 1; gi < 8; ++gi) s += join[gi * 128 + te];
                 slab[(long)S * cs.Ko * Kgemm + (long)split * cs.Ko + row] = s;
             }
         }
@@ -2482,15 +2738,158 @@ static WgradPlan plan_wgrad(const ConvShape& cs, long M, bool want_bias,
     return p;
 }
 
+// the wide_dma leaves' carried-row twins, [DEPTH 64][bias][pad > 0].  The
+// automatic plan reaches three of them (plan_wgrad_kloop); the four DEPTH 32
+// ones and <64, false, false> measured slower or no faster than decode and
+// exist for A/B runs only (walk = 1, tools/bench_kernels.py --wgradwalk).
+using WgradWalkKernel = void (*)(const bf16*, const bf16*, float*, ConvShape,
+                                 long, int, int, WgradWalk);
+static const WgradWalkKernel WGRAD_WALK_KERNELS[2][2][2] = {
+    {{k_conv_wgrad_wide_walk<32, false, false>,
+      k_conv_wgrad_wide_walk<32, false, true>},
+     {k_conv_wgrad_wide_walk<32, true, false>,
+      k_conv_wgrad_wide_walk<32, true, true>}},
+    {{k_conv_wgrad_wide_walk<64, false, false>,
+      k_conv_wgrad_wide_walk<64, false, true>},
+     {k_conv_wgrad_wide_walk<64, true, false>,
+      k_conv_wgrad_wide_walk<64, true, true>}},
+};
+
+// DDPX_WGRAD_WALK, read once per process: "0" keeps the automatic plan on
+// the decode loop (A/B runs)
+static bool wgrad_walk_env_off() {
+    static const char* v = getenv("DDPX_WGRAD_WALK");
+    return v && v[0] == '0' && v[1] == 0;
+}
+
+// The tile step of a wide_dma leaf as (dn, dp, dq) and as byte steps.  The
+// sums are formed in long; plan_wgrad_kloop checks that they fit.
+static bool make_wgrad_walk(const ConvShape& cs, long M, const WgradPlan& plan,
+                            WgradWalk* out) {
+    const int depth = plan.leaf == WgradLeaf::WideDma64 ? 64 : 32;
+    const long m_step = (long)plan.S * depth;
+    const long PQ = (long)cs.P * cs.Q;
+    const long dn = m_step / PQ, rem = m_step % PQ;
+    const long dp = rem / cs.Q, dq = rem % cs.Q;
+    const long st = cs.stride, WC = (long)cs.W * cs.C;
+    const long d0 = 2 * (dn * cs.H * WC + dp * st * WC + dq * st * cs.C);
+    const long d1 = 2 * ((long)cs.W - cs.Q) * st * cs.C;
+    const long d2 = 2 * ((long)cs.H - cs.P * st) * WC;
+    const long ystep = 2 * m_step * cs.Ko;
+    const long lim = INT_MAX;
+    auto fits = [&](long v) { return v > -lim && v < lim; };
+    // the row counter the first decode takes is unsigned 32-bit; the per-tile
+    // x step, with either or both carries, and the dy step are ints; the
+    // offsets themselves are 64-bit
+    const bool ok = M + m_step < lim && fits(d0) && fits(d0 + d1) &&
+                    fits(d0 + d2) && fits(d0 + d1 + d2) && fits(d2) &&
+                    fits(ystep) && 2L * 48 * cs.Ko < lim;
+    if (out)
+        *out = WgradWalk{(int)dn, (int)dp, (int)dq, ok ? (int)d0 : 0,
+                         ok ? (int)d1 : 0, ok ? (int)d2 : 0,
+                         ok ? (int)ystep : 0};
+    return ok;
+}
+
+// K loop of the wgrad MFMA launch: "walk" (carried rows,
+// k_conv_wgrad_wide_walk) or "decode" (per-tile row decode).  The one place
+// that decides; pure host arithmetic.  walk: -1 automatic, 0 decode, 1 forces
+// walk; a forced walk on a shape it does not fit runs decode, and the plan
+// says so.  Walk fits the wide_dma leaves only, with M + S*DEPTH and the
+// per-tile byte steps inside an int (make_wgrad_walk).  wk, if given, gets
+// the tile step of a wide_dma leaf whatever the loop (zeros for other
+// leaves).
+//
+// Automatic (unless DDPX_WGRAD_WALK=0) walks a class only where its median
+// beat decode in two separate runs of tools/bench_kernels.py --wgradwalk
+// (profiles/bench_kernels_wgradwalk.log; walk / decode, run A, run B):
+//   <64, bias, pad 0>      conv3 0.976 0.980, conv4 0.919 0.920   walk
+//   <64, bias, pad > 0>    VGG 256x56x56 0.933 0.938              walk
+//   <64, no bias, pad > 0> VGG 256x56x56 0.984 0.986              walk
+//   <64, no bias, pad 0>   conv3 1.002 0.998, conv4 0.877 0.876   decode:
+//                          conv3 was not faster in run A
+//   <32, bias, pad 0>      conv2 1.050 1.053                      decode
+//   <32, *> otherwise      not measured                           decode
+static const char* plan_wgrad_kloop(const ConvShape& cs, long M,
+                                    const WgradPlan& plan, long walk,
+                                    WgradWalk* wk = nullptr) {
+    TORCH_CHECK(walk >= -1 && walk <= 1, "conv wgrad walk must be -1 "
+                "(automatic), 0 (decode) or 1 (walk); got ", walk);
+    if (wk) *wk = WgradWalk{};
+    if (plan.leaf != WgradLeaf::WideDma32 && plan.leaf != WgradLeaf::WideDma64)
+        return "decode";
+    const bool fits = make_wgrad_walk(cs, M, plan, wk);
+    const bool routed = plan.leaf == WgradLeaf::WideDma64 &&
+                        (plan.fused_bias || cs.pad > 0);
+    if (!fits || walk == 0 ||
+        (walk < 0 && (wgrad_walk_env_off() || !routed)))
+        return "decode";
+    return "walk";
+}
+
+static ConvShape wgrad_query_shape(long N, long C, long H, long W, long Ko,
+                                   long R, long S, long stride, long pad) {
+    TORCH_CHECK(N > 0 && C > 0 && Ko > 0 && R > 0 && S > 0 && stride > 0 &&
+                pad >= 0 && H + 2 * pad >= R && W + 2 * pad >= S);
+    return make_shape((int)N, (int)C, (int)H, (int)W, (int)Ko, (int)R, (int)S,
+                      (int)stride, (int)pad);
+}
+
+// (loop name, dn, dp, dq) that conv2d_wgrad[_bias] would run for this shape
+// and walk argument; (dn, dp, dq) is the tile step of a wide_dma leaf, zeros
+// for any other leaf.  Launches nothing.
+std::tuple<std::string, long, long, long> conv2d_wgrad_kloop_plan(
+        long N, long C, long H, long W, long Ko, long R, long S, long stride,
+        long pad, bool want_bias, long walk) {
+    ConvShape cs = wgrad_query_shape(N, C, H, W, Ko, R, S, stride, pad);
+    const long M = (long)cs.N * cs.P * cs.Q;
+    const WgradPlan p = plan_wgrad(cs, M, want_bias, wgrad_override());
+    WgradWalk wk;
+    const char* name = plan_wgrad_kloop(cs, M, p, walk, &wk);
+    return std::make_tuple(std::string(name), (long)wk.dn, (long)wk.dp,
+                           (long)wk.dq);
+}
+
+// The (n, p, q, valid) the carried-row state yields for one lane row: GEMM
+// row split*DEPTH + chunk_row of a block's first tile, then `tiles` steps of
+// wgrad_walk_step.  valid = the row is below M.  wide_dma shapes only.
+std::vector<std::tuple<long, long, long, bool>> conv2d_wgrad_walk_rows(
+        long N, long C, long H, long W, long Ko, long R, long S, long stride,
+        long pad, bool want_bias, long split, long chunk_row, long tiles) {
+    ConvShape cs = wgrad_query_shape(N, C, H, W, Ko, R, S, stride, pad);
+    const long M = (long)cs.N * cs.P * cs.Q;
+    const WgradPlan p = plan_wgrad(cs, M, want_bias, wgrad_override());
+    WgradWalk wk{};
+    TORCH_CHECK((p.leaf == WgradLeaf::WideDma32 ||
+                 p.leaf == WgradLeaf::WideDma64) &&
+                make_wgrad_walk(cs, M, p, &wk),
+                "conv2d_wgrad_walk_rows: the shape does not take the walk");
+    const int depth = p.leaf == WgradLeaf::WideDma64 ? 64 : 32;
+    TORCH_CHECK(split >= 0 && split < p.S && chunk_row >= 0 &&
+                chunk_row < depth && tiles >= 0);
+    const unsigned st = cs.stride, Qs = cs.Q * st, Ps = cs.P * st;
+    long gm = split * depth + chunk_row;
+    long n = gm / ((long)cs.P * cs.Q);
+    unsigned ub = (unsigned)(gm % cs.Q) * st - Qs;
+    unsigned vb = (unsigned)(gm / cs.Q % cs.P) * st - Ps;
+    std::vector<std::tuple<long, long, long, bool>> rows;
+    for (long t = 0; t < tiles; ++t) {
+        rows.emplace_back(n, (long)((vb + Ps) / st), (long)((ub + Qs) / st),
+                          gm < M);
+        bool c1, c2;
+        wgrad_walk_step(ub, vb, wk.dq * st, Qs, wk.dp * st, st, Ps, c1, c2);
+        n += wk.dn + c2;
+        gm += (long)p.S * depth;
+    }
+    return rows;
+}
+
 // (leaf name, split, fused_bias) that conv2d_wgrad / conv2d_wgrad_bias would
 // run for this shape under this process's DDPX_WGRAD_V; launches nothing
 std::tuple<std::string, long, bool> conv2d_wgrad_plan(
         long N, long C, long H, long W, long Ko, long R, long S, long stride,
         long pad, bool want_bias) {
-    TORCH_CHECK(N > 0 && C > 0 && Ko > 0 && R > 0 && S > 0 && stride > 0 &&
-                pad >= 0 && H + 2 * pad >= R && W + 2 * pad >= S);
-    ConvShape cs = make_shape((int)N, (int)C, (int)H, (int)W, (int)Ko, (int)R,
-                              (int)S, (int)stride, (int)pad);
+    ConvShape cs = wgrad_query_shape(N, C, H, W, Ko, R, S, stride, pad);
     WgradPlan p = plan_wgrad(cs, (long)cs.N * cs.P * cs.Q, want_bias,
                              wgrad_override());
     return std::make_tuple(std::string(WGRAD_LEAVES[(int)p.leaf].name),
@@ -2504,13 +2903,15 @@ std::tuple<std::string, long, bool> conv2d_wgrad_plan(
 static std::vector<at::Tensor> wgrad_impl(const at::Tensor& dy,
                                           const at::Tensor& x, long R,
                                           long S, long stride, long pad,
-                                          bool want_bias) {
+                                          bool want_bias, long walk) {
     ConvShape cs = make_shape(x, dy.size(1), (int)R, (int)S, (int)stride,
                               (int)pad);
     TORCH_CHECK(cs.P == dy.size(2) && cs.Q == dy.size(3));
     const long M = (long)cs.N * cs.P * cs.Q;
     const int Kgemm = cs.R * cs.S * cs.C;
     const WgradPlan plan = plan_wgrad(cs, M, want_bias, wgrad_override());
+    WgradWalk wk;
+    const bool walks = plan_wgrad_kloop(cs, M, plan, walk, &wk)[0] == 'w';
     const int S_ = plan.S;
     const bool fused_bias = plan.fused_bias;
 
@@ -2580,10 +2981,17 @@ static std::vector<at::Tensor> wgrad_impl(const at::Tensor& dy,
         const long total = (long)cs.Ko * Kgemm;
         const long bias_ld = fused_bias ? cs.Ko : 0;
         auto slab = at::empty({S_ * (total + bias_ld)}, f32);
-        hipLaunchKernelGGL(WGRAD_LEAVES[(int)plan.leaf].kern[fused_bias],
-                           dim3(plan.gk, plan.gr, S_), dim3(256), 0,
-                           stream.stream(), dyp, xp, slab.data_ptr<float>(),
-                           cs, M, Kgemm, S_);
+        if (walks)
+            hipLaunchKernelGGL(
+                WGRAD_WALK_KERNELS[plan.leaf == WgradLeaf::WideDma64]
+                                  [fused_bias][cs.pad > 0],
+                dim3(plan.gk, plan.gr, S_), dim3(256), 0, stream.stream(),
+                dyp, xp, slab.data_ptr<float>(), cs, M, Kgemm, S_, wk);
+        else
+            hipLaunchKernelGGL(WGRAD_LEAVES[(int)plan.leaf].kern[fused_bias],
+                               dim3(plan.gk, plan.gr, S_), dim3(256), 0,
+                               stream.stream(), dyp, xp,
+                               slab.data_ptr<float>(), cs, M, Kgemm, S_);
         HIP_CHECK_LAST();
         at::Tensor slab_f = slab;
         int S_c = S_;
@@ -2617,14 +3025,14 @@ static std::vector<at::Tensor> wgrad_impl(const at::Tensor& dy,
 }
 
 at::Tensor conv2d_wgrad(at::Tensor dy, at::Tensor x, long R, long S,
-                        long stride, long pad) {
-    return wgrad_impl(dy, x, R, S, stride, pad, false)[0];
+                        long stride, long pad, long walk) {
+    return wgrad_impl(dy, x, R, S, stride, pad, false, walk)[0];
 }
 
 // dw as conv2d_wgrad (bit-identical on the MFMA leaves), plus the bias
 // gradient db[ko] = sum over (n, p, q) of dy, fp32
 std::vector<at::Tensor> conv2d_wgrad_bias(at::Tensor dy, at::Tensor x,
                                           long R, long S, long stride,
-                                          long pad) {
-    return wgrad_impl(dy, x, R, S, stride, pad, true);
+                                          long pad, long walk) {
+    return wgrad_impl(dy, x, R, S, stride, pad, true, walk);
 }

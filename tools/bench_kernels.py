@@ -7,6 +7,7 @@ Usage (on a GPU box):  python tools/bench_kernels.py [--resnet]
                        python tools/bench_kernels.py --wgraddma [--leaves wt3]
                        python tools/bench_kernels.py --dgradtaps
                        python tools/bench_kernels.py --kwalk
+                       python tools/bench_kernels.py --wgradwalk
                        python tools/bench_kernels.py --stem
                        python tools/bench_kernels.py --linear
                        python tools/bench_kernels.py --dwconv [--trs 4,8,32]
@@ -506,6 +507,62 @@ def bench_kwalk(rounds):
         torch.cuda.empty_cache()
 
 
+VGG_L3 = ("vgg256", 64, 256, 56, 56, 256, 3, 1, 1)
+
+
+def bench_wgradwalk(rounds):
+    """Tile loop of the wide wgrad leaves: per-tile row decode (walk 0)
+    against carried rows (walk 1), alternated in one process (`walk` is an
+    argument).  Toy_Net's conv2, conv3 and conv4 at B = 1024 go through
+    conv2d_wgrad_bias as the training step calls them; r18s1 (not a wide
+    leaf: both sides run decode, a control) and one VGG layer with pad 1 run
+    without bias.  Three more rows complete the (DEPTH 64) x (bias) x (pad)
+    classes the automatic plan decides on: conv3 and conv4 without bias, the
+    VGG layer with bias.  dw (and db) are checked torch.equal before timing;
+    30 warm-up calls, then device events around 10 calls, median/min/max over
+    `rounds`."""
+    ext = load_extension(required=True)
+    dev = torch.device("cuda:0")
+    by_name = {s[0]: s for s in TOYNET + RESNET + [VGG_L3]}
+    rows = [("conv2", True), ("conv3", True), ("conv4", True),
+            ("r18s1", False), ("vgg256", False),
+            ("conv3", False), ("conv4", False), ("vgg256", True)]
+    print(f"{'shape':8s} {'bias':>4s} {'pad':>3s} {'leaf':13s} {'walk':>4s} "
+          f"{'plan':7s} {'med us':>9s} {'min':>9s} {'max':>9s} "
+          f"{'vs decode':>9s} {'TFLOP/s':>8s}")
+    for name, bias in rows:
+        _, N, C, H, W, K, R, stride, pad = by_name[name]
+        P = (H + 2 * pad - R) // stride + 1
+        flops = 2.0 * N * P * P * K * C * R * R
+        g = torch.Generator(device=dev).manual_seed(0)
+        x = torch.randn(N, C, H, W, device=dev, generator=g) \
+            .to(torch.bfloat16).contiguous(memory_format=CL)
+        dy = torch.randn(N, K, P, P, device=dev, generator=g) \
+            .to(torch.bfloat16).contiguous(memory_format=CL)
+        geom = (N, C, H, W, K, R, R, stride, pad, bias)
+        leaf = ext.conv2d_wgrad_plan(*geom)[0]
+        if bias:
+            call = (lambda wk: ext.conv2d_wgrad_bias(dy, x, R, R, stride,
+                                                     pad, wk))
+        else:
+            call = (lambda wk: [ext.conv2d_wgrad(dy, x, R, R, stride, pad,
+                                                 wk)])
+        for a, b in zip(call(0), call(1)):
+            if a is not None and not torch.equal(a, b):
+                raise RuntimeError(f"wgrad {name}: walk differs from decode")
+        res = _time_alternating({wk: (lambda wk=wk: call(wk))
+                                 for wk in (0, 1)}, rounds=rounds, warmup=30)
+        for wk in (0, 1):
+            med, lo, hi = res[wk]
+            plan = ext.conv2d_wgrad_kloop_plan(*geom, wk)[0]
+            print(f"{name:8s} {int(bias):4d} {pad:3d} {leaf:13s} {wk:4d} "
+                  f"{plan:7s} {med:9.1f} {lo:9.1f} {hi:9.1f} "
+                  f"{med / res[0][0]:9.3f} {flops / med / 1e6:8.1f}",
+                  flush=True)
+        del x, dy
+        torch.cuda.empty_cache()
+
+
 def bench_linear(rounds):
     """The linear layers' three products through their whole entry points
     (transposes and slab combines included): the legacy path (impl 0)
@@ -818,6 +875,7 @@ def main():
                     help="conv2d_dgrad group values for --dgradtaps, raster "
                          "(0) first")
     ap.add_argument("--kwalk", action="store_true")
+    ap.add_argument("--wgradwalk", action="store_true")
     ap.add_argument("--stem", action="store_true")
     ap.add_argument("--linear", action="store_true")
     ap.add_argument("--resnet", action="store_true")
@@ -851,6 +909,9 @@ def main():
         return
     if args.kwalk:
         bench_kwalk(rounds=30)
+        return
+    if args.wgradwalk:
+        bench_wgradwalk(rounds=30)
         return
     if args.stem:
         bench_stem(rounds=30)
