@@ -30,6 +30,7 @@ SOURCES = [
     "conv.hip",
     "dwconv.hip",
     "gconv.hip",
+    "gn.hip",
     "data.hip",
 ]
 

@@ -961,6 +961,80 @@ def batch_norm(x, running_mean, running_var, weight, bias,
     return y.to(x.dtype) if x.is_cuda and amp_mod.is_enabled() else y
 
 
+# ------------------------------------------------------------- group norm ---
+
+class _HIPGroupNorm(torch.autograd.Function):
+    """GroupNorm over 4-D channels_last bf16 activations with the fused
+    relu(norm(x) + residual) epilogue (ops/hip/gn.hip).  Statistics are per
+    (image, group); there are no running buffers, so train and eval are one
+    computation — only the relu mask is skipped when no backward will run."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, num_groups, eps, fuse_relu, residual):
+        ext = require_ext_for(x)
+        xb = _chlast(_to_bf16(x))
+        rb = None if residual is None else _chlast(_to_bf16(residual))
+        # (grad mode is off inside Function.forward: needs_input_grad tells
+        # whether a backward will run)
+        want_mask = any(ctx.needs_input_grad)
+        y, mean, invstd, mask = ext.gn_fwd(
+            xb, weight.detach(), bias.detach(), num_groups, eps, fuse_relu,
+            rb, want_mask)
+        ctx.save_for_backward(xb, weight, mean, invstd, mask)
+        ctx.num_groups = num_groups
+        ctx.fuse_relu = fuse_relu
+        ctx.x_dtype = x.dtype
+        ctx.has_residual = residual is not None
+        # skip-grad fusion arming, exactly as _HIPBatchNorm
+        ctx.skip_armed = False
+        if (residual is not None and residual.is_cuda
+                and residual.dtype == torch.bfloat16 and _skipfuse_on()
+                and residual.requires_grad):
+            sb = getattr(residual, "_ddpx_skipbox", None)
+            if sb is not None:
+                ctx.skip_armed = True
+                ctx.skip_stash = sb
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xb, weight, mean, invstd, mask = ctx.saved_tensors
+        ext = require_ext_for(dy)
+        dyb = _chlast(_to_bf16(dy))
+        out = ext.gn_bwd(xb, dyb, weight.detach(), mean, invstd, mask,
+                         ctx.num_groups, ctx.fuse_relu, ctx.has_residual)
+        dx, dweight, dbias = out[0], out[1], out[2]
+        dresid = out[3] if ctx.has_residual else None
+        if ctx.x_dtype == torch.float32:
+            dx = dx.float()
+        if dresid is not None and ctx.skip_armed:
+            stash = ctx.skip_stash
+            prev = stash.get("g")
+            stash["g"] = dresid if prev is None else prev + dresid
+            dresid = None   # delivered through the junction conv's dgrad
+        return dx, dweight, dbias, None, None, None, dresid
+
+
+def group_norm(x, num_groups, weight, bias, eps=1e-5, fuse_relu=False,
+               residual=None):
+    """GroupNorm with optionally fused ReLU and residual add:
+    relu(gn(x) + residual).  4-D GPU input with C % 8 == 0 and affine
+    parameters runs the HIP kernels; anything else the torch formula (the
+    same scope rule as batch_norm's C % 8)."""
+    if (x.is_cuda and x.dim() == 4 and x.shape[1] % 8 == 0
+            and weight is not None and bias is not None
+            and require_ext_for(x) is not None):
+        return _HIPGroupNorm.apply(x, weight, bias, num_groups, eps,
+                                   fuse_relu, residual)
+    xf = x.float() if x.dtype != torch.float32 else x
+    y = F.group_norm(xf, num_groups, weight, bias, eps)
+    if residual is not None:
+        y = y + residual.float()
+    if fuse_relu:
+        y = F.relu(y)
+    return y.to(x.dtype) if x.is_cuda and amp_mod.is_enabled() else y
+
+
 # -------------------------------------------------------- sync batch norm ---
 
 def _gather_rows(row, group, native):
@@ -1527,7 +1601,13 @@ def conv_bn(conv_mod, bn_mod, x, residual=None, pool=None):
     pool: the MaxPool2d module that consumes the BN output, if any.  A
     training BN(fuse_relu) -> MaxPool2d(2) junction over even extents runs
     as the fused BN+ReLU+pool2 kernels (``DDPX_BNPOOL=0`` opts out);
-    anything else is exactly ``pool(bn(conv(x)))``."""
+    anything else is exactly ``pool(bn(conv(x)))``.
+
+    A ``GroupNorm`` in the BN's place takes the plain conv — no statistics
+    slab — then ``norm(y, residual)`` and the pool, unfused."""
+    if getattr(bn_mod, "is_group_norm", False):
+        out = bn_mod(conv_mod(x), residual=residual)
+        return out if pool is None else pool(out)
     use_stats = (x.is_cuda and require_ext_for(x) is not None
                  and bn_mod.training and getattr(conv_mod, "dilation",
                                                  (1, 1)) in ((1, 1), 1))

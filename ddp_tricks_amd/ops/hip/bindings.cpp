@@ -204,6 +204,18 @@ std::tuple<std::string, long, long, long, long, long> gconv2d_plan(
     std::string op, long N, long C, long H, long W, long groups, long stride,
     long pad);
 
+// gn.hip
+std::vector<at::Tensor> gn_fwd(at::Tensor x, at::Tensor gamma, at::Tensor beta,
+                               long G, double eps, bool fuse_relu,
+                               c10::optional<at::Tensor> residual,
+                               bool want_mask, long strips);
+std::vector<at::Tensor> gn_bwd(at::Tensor x, at::Tensor dy, at::Tensor gamma,
+                               at::Tensor mean, at::Tensor invstd,
+                               at::Tensor mask, long G, bool fuse_relu,
+                               bool has_residual, long strips);
+std::tuple<long, long, long, long> gn_plan(long N, long C, long H, long W,
+                                           long strips);
+
 // data.hip
 std::vector<at::Tensor> batch_gather_aug(at::Tensor store, at::Tensor labels,
                                          at::Tensor index, at::Tensor lut,
@@ -462,6 +474,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "input; launches nothing",
           py::arg("op"), py::arg("N"), py::arg("C"), py::arg("H"),
           py::arg("W"), py::arg("groups"), py::arg("stride"), py::arg("pad"));
+    m.def("gn_fwd", &gn_fwd,
+          "GroupNorm forward over bf16 channels_last x with the fused "
+          "relu(norm(x) + residual) epilogue: (y, mean [N,G], invstd [N,G], "
+          "mask); the packed relu mask is written only with fuse_relu and "
+          "want_mask; strips > 0 forces the strip count",
+          py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("G"),
+          py::arg("eps"), py::arg("fuse_relu") = false,
+          py::arg("residual") = c10::nullopt, py::arg("want_mask") = true,
+          py::arg("strips") = -1);
+    m.def("gn_bwd", &gn_bwd,
+          "GroupNorm backward: (dx, dgamma, dbeta[, dresid])",
+          py::arg("x"), py::arg("dy"), py::arg("gamma"), py::arg("mean"),
+          py::arg("invstd"), py::arg("mask"), py::arg("G"),
+          py::arg("fuse_relu") = false, py::arg("has_residual") = false,
+          py::arg("strips") = -1);
+    m.def("gn_plan", &gn_plan,
+          "(chunks per slice, row walkers, strips, channel slices) of the "
+          "GroupNorm kernels over an [N,C,H,W] input; strips > 0 forces the "
+          "strip count, clamped to H*W; launches nothing",
+          py::arg("N"), py::arg("C"), py::arg("H"), py::arg("W"),
+          py::arg("strips") = -1);
     m.def("conv2d_kloop_plan", &conv2d_kloop_plan,
           "'walk' or 'decode': the K loop conv2d_fwd[_stats] (mode 0) or "
           "conv2d_dgrad (mode 1) would run for this shape; kwalk -1 "

@@ -110,6 +110,27 @@ class SyncBatchNorm(nn.modules.batchnorm._BatchNorm, _BatchNormBase):
             residual=residual, pre_stats=pre_stats)
 
 
+class GroupNorm(nn.GroupNorm):
+    """``nn.GroupNorm`` (same parameters and state_dict keys) on the HIP
+    GroupNorm kernels, with BatchNorm2d's fused epilogue flags so it drops
+    into the same call sites: ``forward(x, residual)`` is
+    relu?(gn(x) + residual).  Statistics are per (image, group): no running
+    buffers, no cross-rank traffic, the same computation in train and eval."""
+
+    is_group_norm = True
+
+    def __init__(self, *args, fuse_relu: bool = False, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.fuse_relu = fuse_relu
+
+    def forward(self, x, residual=None, pre_stats=None):
+        # pre_stats: per-channel batch partials of a conv epilogue are of no
+        # use to per-image statistics; accepted for call-site parity, ignored
+        return F_ops.group_norm(x, self.num_groups, self.weight, self.bias,
+                                self.eps, fuse_relu=self.fuse_relu,
+                                residual=residual)
+
+
 class ReLU(nn.ReLU):
     def forward(self, x):
         return F_ops.relu(x, inplace=self.inplace)

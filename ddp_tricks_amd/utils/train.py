@@ -73,6 +73,21 @@ def resolve_model_kwargs(args, model_name: str, dataset_name: str) -> dict:
     return model_kwargs
 
 
+def build_train_model(args, model_name: str, model_kwargs: dict):
+    """The model of this run, before it moves to its device: ``build_model``,
+    and with ``--norm gn`` every BatchNorm2d converted to a GroupNorm on the
+    same weight / bias Parameters (the running buffers go).  The default
+    constructs and calls nothing new."""
+    model = build_model(model_name, **model_kwargs)
+    if (getattr(args, "norm", None) or "bn") == "gn":
+        if getattr(args, "sync_bn", False):
+            raise ValueError("--norm gn and --sync_bn exclude each other")
+        from ..parallel.group_norm import convert_group_norm
+        model = convert_group_norm(
+            model, int(getattr(args, "gn_groups", None) or 32))
+    return model
+
+
 def train(args):
     local_rank = getattr(args, "local_rank", 0) or 0
     device = _resolve_device(local_rank)
@@ -167,7 +182,7 @@ def train(args):
     # Model (seeded identically on all ranks before the DDP broadcast —
     # reference utils/train.py:34-36, README rationale)
     same_seeds(args.seed_num)
-    model = build_model(model_name, **model_kwargs)
+    model = build_train_model(args, model_name, model_kwargs)
     model = model.to(device)
     if getattr(args, "sync_bn", False):
         # opt-in cross-rank BatchNorm statistics; parameters and buffers

@@ -66,6 +66,14 @@ def parse_args():
                         help="convert every BatchNorm to SyncBatchNorm: "
                              "batch statistics over all ranks, one small "
                              "gather per layer and direction")
+    parser.add_argument("--norm", default="bn", type=str,
+                        choices=("bn", "gn"),
+                        help="gn: convert every BatchNorm2d to GroupNorm "
+                             "(per-image statistics: small per-rank batches, "
+                             "no cross-rank traffic, no running buffers)")
+    parser.add_argument("--gn_groups", default=32, type=int,
+                        help="--norm gn: number of groups; must divide every "
+                             "converted layer's channel count")
     parser.add_argument("--label_smoothing", default=0.0, type=float,
                         help="label smoothing of the training loss, in "
                              "[0, 1); validation loss stays unsmoothed")
@@ -99,6 +107,9 @@ def parse_args():
                              "counter hash of (seed, rank, epoch, call), "
                              "fused into the linear epilogue (0 = off)")
     args = parser.parse_args()
+    if args.norm == "gn" and args.sync_bn:
+        parser.error("--norm gn leaves no BatchNorm2d for --sync_bn to "
+                     "convert; pass one of them")
     if args.local_rank is None:
         args.local_rank = int(os.environ.get("LOCAL_RANK", 0))
     return args

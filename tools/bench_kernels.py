@@ -855,8 +855,128 @@ def bench_gconv(rounds):
         torch.cuda.empty_cache()
 
 
+# ResNet-50 norm shapes (C, H) for --gn
+GN_SHAPES = [(64, 112), (256, 56), (512, 28), (1024, 14), (2048, 7)]
+
+
+def bench_gn(rounds):
+    """GroupNorm kernels (gn.hip), G = 32, relu + residual, at B = 32 and 256,
+    forward and backward apart, against (a) torch's F.group_norm + add + relu
+    (its autograd for the backward) on the same bf16 channels_last tensors and
+    (b) this project's bn_fwd_train / bn_bwd at the same shape; alternated in
+    one process, 30 warm-up calls, device events around 10 calls.  Each row:
+    median us (min-max), the share of the HBM-bound time of the least traffic
+    at 8 TB/s (forward: x twice + y; backward: x and dy twice + dx; residual,
+    dresid and mask not counted), the comparisons' medians and their ratio to
+    ours, and the size of x: a share above 100 % can only come from second
+    reads served by the Infinity Cache (256 MiB).  Every output is checked
+    against torch's fp32 formula before timing."""
+    ext = load_extension(required=True)
+    dev = torch.device("cuda:0")
+    G, eps = 32, 1e-5
+    Fn = torch.nn.functional
+    print(f"{'B':>4s} {'C':>5s} {'H':>4s} {'op':4s} {'med us':>8s} {'min':>8s} "
+          f"{'max':>8s} {'%HBM':>6s} {'torch us':>9s} {'torch/ours':>10s} "
+          f"{'bn us':>8s} {'ours/bn':>8s} {'x MiB':>7s}")
+    for N in (32, 256):
+        for C, H in GN_SHAPES:
+            g = torch.Generator(device=dev).manual_seed(N + C + H)
+
+            def act():
+                return (torch.randn(N, C, H, H, device=dev, generator=g)
+                        .to(torch.bfloat16).contiguous(memory_format=CL))
+            x, r, dy = act() * 1.5 + 0.5, act(), act()
+            gam = torch.rand(C, device=dev, generator=g) + 0.5
+            bet = torch.rand(C, device=dev, generator=g) - 0.5
+            rm, rv = torch.zeros(C, device=dev), torch.ones(C, device=dev)
+            y, mean, invstd, mask = ext.gn_fwd(x, gam, bet, G, eps, True, r)
+            _, bm, bi, bmask = ext.bn_fwd_train(x, gam, bet, rm, rv, 0.1, eps,
+                                                True, r, None)
+            xt, rt = x.clone().requires_grad_(True), r.clone().requires_grad_(True)
+            gt, bt = (gam.bfloat16().requires_grad_(True),
+                      bet.bfloat16().requires_grad_(True))
+
+            def t_fwd():
+                return Fn.relu(Fn.group_norm(xt, G, gt, bt, eps) + rt)
+            yt = t_fwd()
+
+            def t_bwd():
+                return torch.autograd.grad(yt, (xt, gt, bt, rt), dy,
+                                           retain_graph=True)
+            ours_b = ext.gn_bwd(x, dy, gam, mean, invstd, mask, G, True, True)
+            # every output, max error: y and dx against torch's fp32 formula
+            # on the GPU to a bf16 ulp (2^-8 of the element, plus 2^-12 of
+            # the largest for the fp32 sums on either side), dgamma and
+            # dbeta against float64 sums to 2^-10 of the largest, the mask
+            # wherever |v| > 2^-10, dresid exactly.  The reference backward takes our mask as
+            # dy_eff: torch's own bf16 path rounds norm(x) before its relu
+            # and flips borderline bits.
+            xf = x.float().requires_grad_(True)
+            gf, bf = gam.clone().requires_grad_(True), \
+                bet.clone().requires_grad_(True)
+            v = Fn.group_norm(xf, G, gf, bf, eps) + r.float()
+            bits = ((mask.view(N, H, H, C // 8, 1) >> torch.arange(
+                8, device=dev, dtype=torch.uint8)) & 1).bool() \
+                .reshape(N, H, H, C).permute(0, 3, 1, 2)
+            ge = dy.float() * bits
+            refs = list(torch.autograd.grad(v, (xf, gf, bf), ge))
+            v = v.detach()
+            # dgamma, dbeta: float64 sums (torch's fp32 ones drift at B = 256)
+            xg = x.double().reshape(N, G, -1)
+            xh = ((xg - xg.mean(2, keepdim=True))
+                  / (xg.var(2, unbiased=False, keepdim=True) + eps).sqrt())
+            refs[1] = (ge.double() * xh.reshape(N, C, H, H)).sum((0, 2, 3))
+            refs[2] = ge.double().sum((0, 2, 3))
+            del xg, xh
+            live = v.abs() > 2.0 ** -10
+            checks = [("mask", bits[live] == (v > 0)[live], None, 0),
+                      ("dresid", ours_b[3].float(), ge, 0),
+                      ("y", y.float(), v.clamp_min(0), 2.0 ** -8),
+                      ("dx", ours_b[0].float(), refs[0], 2.0 ** -8),
+                      ("dgamma", ours_b[1].double(), refs[1], 0),
+                      ("dbeta", ours_b[2].double(), refs[2], 0)]
+            for name, got, ref, rel in checks:
+                if ref is None:
+                    ok = bool(got.all())
+                elif name == "dresid":
+                    ok = torch.equal(got, ref)
+                else:
+                    slack = ref.abs().max() * (2.0 ** -12 if rel else
+                                               2.0 ** -10)
+                    ok = bool(((got - ref).abs()
+                               <= rel * ref.abs() + slack).all())
+                if not ok:
+                    raise RuntimeError(f"gn {name} B{N} C{C} H{H} differs "
+                                       "from the fp32 reference")
+            del xf, v, bits, ge, refs, live, checks
+            xb = x.numel() * 2
+            ops = {
+                "fwd": (lambda: ext.gn_fwd(x, gam, bet, G, eps, True, r),
+                        lambda: t_fwd(),
+                        lambda: ext.bn_fwd_train(x, gam, bet, rm, rv, 0.1, eps,
+                                                 True, r, None), 3 * xb),
+                "bwd": (lambda: ext.gn_bwd(x, dy, gam, mean, invstd, mask, G,
+                                           True, True),
+                        t_bwd,
+                        lambda: ext.bn_bwd(x, dy, gam, bm, bi, bmask, True,
+                                           True, None, False), 5 * xb),
+            }
+            for name, (ours, theirs, bn, traffic) in ops.items():
+                res = _time_alternating({"ours": ours, "torch": theirs,
+                                         "bn": bn}, rounds=rounds, warmup=30)
+                med, lo, hi = res["ours"]
+                tm, bnm = res["torch"][0], res["bn"][0]
+                print(f"{N:4d} {C:5d} {H:4d} {name:4s} {med:8.1f} {lo:8.1f} "
+                      f"{hi:8.1f} {traffic / HBM_PEAK * 1e6 / med * 100:6.1f} "
+                      f"{tm:9.1f} {tm / med:10.2f} {bnm:8.1f} "
+                      f"{med / bnm:8.2f} {xb / 2 ** 20:7.1f}", flush=True)
+            del x, r, dy, y, yt, xt, rt, ours_b, mask, bmask
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--gn", action="store_true")
     ap.add_argument("--gconv", action="store_true")
     ap.add_argument("--dwconv", action="store_true")
     ap.add_argument("--trs", default="",
@@ -884,6 +1004,9 @@ def main():
     ap.add_argument("--bnpool", action="store_true")
     ap.add_argument("--reps", type=int, default=200)
     args = ap.parse_args()
+    if args.gn:
+        bench_gn(rounds=30)
+        return
     if args.gconv:
         bench_gconv(rounds=30)
         return
