@@ -1,6 +1,7 @@
 from .mobilenet import mobilenet_v1  # noqa: F401
 from .resnet import (  # noqa: F401
     resnet18, resnet34, resnet50, resnext50_32x4d, resnext101_32x8d,
+    se_resnet50, se_resnext50_32x4d,
 )
 from .toy_net import Toy_Net  # noqa: F401
 from .vgg import vgg16_bn  # noqa: F401
@@ -12,6 +13,8 @@ _REGISTRY = {
     "resnet50": resnet50,
     "resnext50_32x4d": resnext50_32x4d,
     "resnext101_32x8d": resnext101_32x8d,
+    "se_resnet50": se_resnet50,
+    "se_resnext50_32x4d": se_resnext50_32x4d,
     "vgg16": vgg16_bn,
     "mobilenet_v1": mobilenet_v1,
 }

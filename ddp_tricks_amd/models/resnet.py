@@ -1,5 +1,5 @@
-"""ResNet-18/34/50 and ResNeXt-50/101 on the framework's HIP-backed modules
-(BASELINE.json configs 4-5).
+"""ResNet-18/34/50, ResNeXt-50/101 and SE-ResNet/ResNeXt-50 on the
+framework's HIP-backed modules (BASELINE.json configs 4-5).
 
 MI355X-first block design: every BN+ReLU pair runs as one fused HIP kernel,
 and each block's closing ``relu(bn(out) + identity)`` is a single kernel via
@@ -17,6 +17,11 @@ interchangeable with stock definitions of the same architecture.
 ResNeXt is the same Bottleneck with a grouped 3x3 (``groups``,
 ``base_width``; torchvision's width rule), served by the grouped MFMA kernels
 (ops/hip/gconv.hip).
+
+SE-ResNet / SE-ResNeXt (``se_reduction``) put a Squeeze-and-Excitation gate on
+each Bottleneck's third conv: bn3 runs without its relu and the block closes
+in the SE junction, relu(u * gate + identity) in one kernel (ops/hip/se.hip).
+The gate's keys are ``se.fc1`` / ``se.fc2``, timm's.
 """
 from __future__ import annotations
 
@@ -26,6 +31,7 @@ import torch.nn as nn
 from ..ops.functional import conv_bn
 from ..ops.modules import (
     AdaptiveAvgPool2d, BatchNorm2d, Conv2d, Identity, Linear, MaxPool2d,
+    SqueezeExcite,
 )
 
 
@@ -61,7 +67,7 @@ class Bottleneck(nn.Module):
     expansion = 4
 
     def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1,
-                 base_width=64):
+                 base_width=64, se_reduction=0):
         super().__init__()
         width = int(planes * base_width / 64) * groups
         self.conv1 = conv1x1(inplanes, width)
@@ -69,7 +75,11 @@ class Bottleneck(nn.Module):
         self.conv2 = conv3x3(width, width, stride, groups)
         self.bn2 = BatchNorm2d(width, fuse_relu=True)
         self.conv3 = conv1x1(width, planes * self.expansion)
-        self.bn3 = BatchNorm2d(planes * self.expansion, fuse_relu=True)
+        # with SE the add and the relu move from bn3 into the SE junction
+        self.bn3 = BatchNorm2d(planes * self.expansion,
+                               fuse_relu=se_reduction == 0)
+        if se_reduction > 0:
+            self.se = SqueezeExcite(planes * self.expansion, se_reduction)
         self.relu = Identity()
         self.downsample = downsample
         self.stride = stride
@@ -78,17 +88,22 @@ class Bottleneck(nn.Module):
         identity = x if self.downsample is None else self.downsample(x)
         out = conv_bn(self.conv1, self.bn1, x)
         out = conv_bn(self.conv2, self.bn2, out)
+        if hasattr(self, "se"):
+            u = conv_bn(self.conv3, self.bn3, out)
+            return self.se(u, residual=identity, fuse_relu=True)
         return conv_bn(self.conv3, self.bn3, out, residual=identity)
 
 
 class ResNet(nn.Module):
     def __init__(self, block, layers, num_classes=1000, cifar_stem=False,
-                 groups=1, width_per_group=64):
+                 groups=1, width_per_group=64, se_reduction=0):
         super().__init__()
         self.inplanes = 64
         # only Bottleneck takes them; the defaults build the plain ResNets
         self.block_kw = ({} if (groups, width_per_group) == (1, 64) else
                          dict(groups=groups, base_width=width_per_group))
+        if se_reduction:
+            self.block_kw["se_reduction"] = se_reduction
         if cifar_stem:
             self.conv1 = Conv2d(3, 64, 3, stride=1, padding=1, bias=False)
             self.maxpool = Identity()
@@ -155,3 +170,13 @@ def resnext50_32x4d(num_classes=1000, cifar_stem=False):
 def resnext101_32x8d(num_classes=1000, cifar_stem=False):
     return ResNet(Bottleneck, [3, 4, 23, 3], num_classes, cifar_stem,
                   groups=32, width_per_group=8)
+
+
+def se_resnet50(num_classes=1000, cifar_stem=False):
+    return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, cifar_stem,
+                  se_reduction=16)
+
+
+def se_resnext50_32x4d(num_classes=1000, cifar_stem=False):
+    return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, cifar_stem,
+                  groups=32, width_per_group=4, se_reduction=16)

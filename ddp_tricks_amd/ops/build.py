@@ -31,6 +31,7 @@ SOURCES = [
     "dwconv.hip",
     "gconv.hip",
     "gn.hip",
+    "se.hip",
     "data.hip",
 ]
 

@@ -1035,6 +1035,96 @@ def group_norm(x, num_groups, weight, bias, eps=1e-5, fuse_relu=False,
     return y.to(x.dtype) if x.is_cuda and amp_mod.is_enabled() else y
 
 
+# -------------------------------------------------- squeeze-and-excitation ---
+
+class _HIPSEScale(torch.autograd.Function):
+    """relu?(u * sigmoid(fc2(relu(fc1(mean_hw u))))[n, c] (+ residual)) over
+    4-D channels_last bf16 activations (ops/hip/se.hip).  The squeeze, the
+    gated epilogue and the two backward passes are SE's kernels; the two tiny
+    FCs run on the linear kernels, called here directly so the whole junction
+    is one autograd node and the squeeze path's gradient dz / HW enters dx
+    inside the kernel instead of being a tensor autograd accumulates."""
+
+    @staticmethod
+    def forward(ctx, u, w1, b1, w2, b2, residual, fuse_relu):
+        ext = require_ext_for(u)
+        ub = _chlast(_to_bf16(u))
+        rb = None if residual is None else _chlast(_to_bf16(residual))
+        w1b = weight_variant(w1, "flat").view(w1.shape[0], -1)
+        w2b = weight_variant(w2, "flat").view(w2.shape[0], -1)
+        z = ext.se_squeeze(ub)
+        h = ext.linear_act_fwd(z, w1b, b1.detach().float(), 0, 1.0, 0)
+        a = ext.linear_fwd(h, w2b, b2.detach().float())
+        want_mask = any(ctx.needs_input_grad)
+        y, mask = ext.se_apply(ub, a, rb, fuse_relu, want_mask)
+        ctx.save_for_backward(ub, a, h, z, mask, w1b, w2b)
+        ctx.fuse_relu = fuse_relu
+        ctx.u_dtype = u.dtype
+        ctx.has_residual = residual is not None
+        ctx.w_meta = (w1.shape, w1.dtype, w2.shape, w2.dtype, b1.dtype,
+                      b2.dtype)
+        # skip-grad fusion arming, exactly as _HIPGroupNorm
+        ctx.skip_armed = False
+        if (residual is not None and residual.is_cuda
+                and residual.dtype == torch.bfloat16 and _skipfuse_on()
+                and residual.requires_grad):
+            sb = getattr(residual, "_ddpx_skipbox", None)
+            if sb is not None:
+                ctx.skip_armed = True
+                ctx.skip_stash = sb
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        ub, a, h, z, mask, w1b, w2b = ctx.saved_tensors
+        w1s, w1t, w2s, w2t, b1t, b2t = ctx.w_meta
+        ext = require_ext_for(dy)
+        dyb = _chlast(_to_bf16(dy))
+        da = ext.se_bwd_gate(dyb, ub, mask, a, ctx.fuse_relu)
+        db2 = ext.col_sum(da)
+        dw2 = ext.linear_wgrad(da, h)
+        dh = ext.relu_drop_bwd(ext.linear_dgrad(da, w2b), h, 1.0)
+        db1 = ext.col_sum(dh)
+        dw1 = ext.linear_wgrad(dh, z)
+        dz = ext.linear_dgrad(dh, w1b)
+        dx, dresid = ext.se_bwd_dx(dyb, ub, mask, a, dz, ctx.fuse_relu,
+                                   ctx.has_residual)
+        if ctx.u_dtype == torch.float32:
+            dx = dx.float()
+        if dresid is not None and ctx.skip_armed:
+            stash = ctx.skip_stash
+            prev = stash.get("g")
+            stash["g"] = dresid if prev is None else prev + dresid
+            dresid = None   # delivered through the junction conv's dgrad
+        return (dx, dw1.view(w1s).to(w1t), db1.to(b1t), dw2.view(w2s).to(w2t),
+                db2.to(b2t), dresid, None)
+
+
+def se_scale(u, fc1_weight, fc1_bias, fc2_weight, fc2_bias, residual=None,
+             fuse_relu=False):
+    """The Squeeze-and-Excitation junction with optionally fused residual add
+    and ReLU: relu?(u * s[n, c] + residual), s = sigmoid(fc2(relu(fc1(z)))),
+    z = mean over (H, W) of u.  The fc weights are [C/r, C(, 1, 1)] and
+    [C, C/r(, 1, 1)].  4-D GPU input with C % 8 == 0 runs the HIP kernels;
+    anything else the same formula in torch (the scope rule of group_norm)."""
+    if (u.is_cuda and u.dim() == 4 and u.shape[1] % 8 == 0
+            and require_ext_for(u) is not None):
+        return _HIPSEScale.apply(u, fc1_weight, fc1_bias, fc2_weight,
+                                 fc2_bias, residual, fuse_relu)
+    uf = u if u.dtype in (torch.float32, torch.float64) else u.float()
+    ft = uf.dtype
+    z = uf.flatten(2).mean(2)
+    h = F.relu(F.linear(z, fc1_weight.flatten(1).to(ft), fc1_bias.to(ft)))
+    s = torch.sigmoid(F.linear(h, fc2_weight.flatten(1).to(ft),
+                               fc2_bias.to(ft)))
+    y = uf * s.view(s.shape + (1,) * (u.dim() - 2))
+    if residual is not None:
+        y = y + residual.to(ft)
+    if fuse_relu:
+        y = F.relu(y)
+    return y.to(u.dtype) if u.is_cuda and amp_mod.is_enabled() else y
+
+
 # -------------------------------------------------------- sync batch norm ---
 
 def _gather_rows(row, group, native):

@@ -216,6 +216,19 @@ std::vector<at::Tensor> gn_bwd(at::Tensor x, at::Tensor dy, at::Tensor gamma,
 std::tuple<long, long, long, long> gn_plan(long N, long C, long H, long W,
                                            long strips);
 
+// se.hip
+at::Tensor se_squeeze(at::Tensor u, long strips);
+std::tuple<at::Tensor, at::Tensor> se_apply(
+    at::Tensor u, at::Tensor a, c10::optional<at::Tensor> residual,
+    bool fuse_relu, bool want_mask);
+at::Tensor se_bwd_gate(at::Tensor dy, at::Tensor u, at::Tensor mask,
+                       at::Tensor a, bool fuse_relu, long strips);
+std::tuple<at::Tensor, c10::optional<at::Tensor>> se_bwd_dx(
+    at::Tensor dy, at::Tensor u, at::Tensor mask, at::Tensor a, at::Tensor dz,
+    bool fuse_relu, bool has_residual);
+std::tuple<long, long, long, long> se_plan(long N, long C, long H, long W,
+                                           long strips);
+
 // data.hip
 std::vector<at::Tensor> batch_gather_aug(at::Tensor store, at::Tensor labels,
                                          at::Tensor index, at::Tensor lut,
@@ -493,6 +506,34 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "(chunks per slice, row walkers, strips, channel slices) of the "
           "GroupNorm kernels over an [N,C,H,W] input; strips > 0 forces the "
           "strip count, clamped to H*W; launches nothing",
+          py::arg("N"), py::arg("C"), py::arg("H"), py::arg("W"),
+          py::arg("strips") = -1);
+    m.def("se_squeeze", &se_squeeze,
+          "Squeeze-and-Excitation squeeze: z [N,C] bf16 = mean over (H, W) of "
+          "bf16 channels_last u (fp32 sums, one division, one rounding); "
+          "strips > 0 forces the strip count",
+          py::arg("u"), py::arg("strips") = -1);
+    m.def("se_apply", &se_apply,
+          "(y, mask): y = relu?(u * sigmoid(a)[n, c] (+ residual)) for bf16 "
+          "gate logits a [N,C]; the packed relu mask is written only with "
+          "fuse_relu and want_mask",
+          py::arg("u"), py::arg("a"), py::arg("residual") = c10::nullopt,
+          py::arg("fuse_relu") = false, py::arg("want_mask") = true);
+    m.def("se_bwd_gate", &se_bwd_gate,
+          "da [N,C] bf16 = (sum_hw g u) s (1 - s), g the relu-masked dy",
+          py::arg("dy"), py::arg("u"), py::arg("mask"), py::arg("a"),
+          py::arg("fuse_relu") = false, py::arg("strips") = -1);
+    m.def("se_bwd_dx", &se_bwd_dx,
+          "(dx, dresid): dx = g s + dz / HW for the squeeze gradient dz "
+          "[N,C]; dresid = g with a residual (dy itself without relu), else "
+          "None",
+          py::arg("dy"), py::arg("u"), py::arg("mask"), py::arg("a"),
+          py::arg("dz"), py::arg("fuse_relu") = false,
+          py::arg("has_residual") = false);
+    m.def("se_plan", &se_plan,
+          "(chunks per slice, row walkers, strips, channel slices) of the SE "
+          "kernels over an [N,C,H,W] input; strips > 0 forces the strip "
+          "count, clamped to H*W; launches nothing",
           py::arg("N"), py::arg("C"), py::arg("H"), py::arg("W"),
           py::arg("strips") = -1);
     m.def("conv2d_kloop_plan", &conv2d_kloop_plan,

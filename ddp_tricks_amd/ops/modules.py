@@ -131,6 +131,31 @@ class GroupNorm(nn.GroupNorm):
                                 residual=residual)
 
 
+class SqueezeExcite(nn.Module):
+    """Squeeze-and-Excitation channel gate with the block's closing residual
+    add and ReLU fused in: ``forward(u, residual, fuse_relu)`` is
+    relu?(u * sigmoid(fc2(relu(fc1(mean_hw u)))) + residual).
+
+    ``fc1`` / ``fc2`` are 1x1 convolutions in name and shape only —
+    ``fc1.weight [C/r, C, 1, 1]``, ``fc2.weight [C, C/r, 1, 1]``, both with
+    bias — so the state_dict keys match timm's ``se.fc1`` / ``se.fc2``; the
+    junction views them as matrices for the linear kernels."""
+
+    def __init__(self, channels: int, reduction: int = 16):
+        super().__init__()
+        hidden = channels // reduction
+        if hidden < 1:
+            raise ValueError(f"SqueezeExcite: channels {channels} // "
+                             f"reduction {reduction} leaves no hidden unit")
+        self.fc1 = nn.Conv2d(channels, hidden, 1)
+        self.fc2 = nn.Conv2d(hidden, channels, 1)
+
+    def forward(self, u, residual=None, fuse_relu=False):
+        return F_ops.se_scale(u, self.fc1.weight, self.fc1.bias,
+                              self.fc2.weight, self.fc2.bias,
+                              residual=residual, fuse_relu=fuse_relu)
+
+
 class ReLU(nn.ReLU):
     def forward(self, x):
         return F_ops.relu(x, inplace=self.inplace)

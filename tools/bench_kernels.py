@@ -12,6 +12,7 @@ Usage (on a GPU box):  python tools/bench_kernels.py [--resnet]
                        python tools/bench_kernels.py --linear
                        python tools/bench_kernels.py --dwconv [--trs 4,8,32]
                        python tools/bench_kernels.py --gconv
+                       python tools/bench_kernels.py --gn | --se
 
 Times conv fwd/dgrad/wgrad per shape with HIP events (200 reps after 20
 warmup) and prints achieved TFLOP/s next to microseconds, so kernel A/B
@@ -974,8 +975,108 @@ def bench_gn(rounds):
             torch.cuda.empty_cache()
 
 
+# SE-ResNeXt-50 junction shapes (C, H) for --se
+SE_SHAPES = [(256, 56), (512, 28), (1024, 14), (2048, 7)]
+
+
+def bench_se(rounds):
+    """The Squeeze-and-Excitation junction (se.hip + the linear kernels),
+    r = 16, relu + residual, at B = 32 and 256: forward and backward of the
+    whole autograd Function against the torch composition (adaptive avg-pool,
+    two F.linear, sigmoid, mul, add, relu, and its autograd) on the same bf16
+    channels_last tensors and bf16 weights; alternated in one process, 30
+    warm-up calls, device events around 10 calls.  Each row: median us
+    (min-max), the share of the HBM-bound time of the least traffic at 8 TB/s
+    (forward 2u + r + y, backward 2dy + 2u + dx + dresid; mask and the [N, C]
+    tensors not counted), torch's median and its ratio to ours, the size of u.
+    Before timing y is checked against the fp32 formula, and dx, dresid and
+    the four parameter gradients against the fp32 formula's autograd with
+    this path's mask as dy_eff."""
+    from ddp_tricks_amd.ops import SqueezeExcite
+    dev = torch.device("cuda:0")
+    Fn = torch.nn.functional
+    print(f"{'B':>4s} {'C':>5s} {'H':>4s} {'op':4s} {'med us':>8s} {'min':>8s} "
+          f"{'max':>8s} {'%HBM':>6s} {'torch us':>9s} {'torch/ours':>10s} "
+          f"{'u MiB':>7s}")
+    for N in (32, 256):
+        for C, H in SE_SHAPES:
+            g = torch.Generator(device=dev).manual_seed(N + C + H)
+
+            def act():
+                return (torch.randn(N, C, H, H, device=dev, generator=g)
+                        .to(torch.bfloat16).contiguous(memory_format=CL))
+            u, r, dy = act().requires_grad_(True), act().requires_grad_(True), act()
+            se = SqueezeExcite(C, 16).to(dev)
+            with torch.no_grad():   # hidden units clear of the relu's edge:
+                # a unit whose sign differs between two roundings of z flips
+                # its whole gradient row, in any implementation
+                se.fc1.bias.copy_(1.0 - 2.0 * (torch.arange(C // 16) % 2))
+            ps = list(se.parameters())
+            wt = [p.detach().flatten(1).bfloat16().requires_grad_(True)
+                  if p.dim() == 4 else p.detach().bfloat16().requires_grad_(True)
+                  for p in ps]
+
+            def ours_fwd():
+                return se(u, residual=r, fuse_relu=True)
+
+            def t_fwd(x=u, res=r, w=wt, relu=True):
+                z = Fn.adaptive_avg_pool2d(x, 1).flatten(1)
+                s = torch.sigmoid(Fn.linear(Fn.relu(Fn.linear(z, w[0], w[1])),
+                                            w[2], w[3]))
+                v = x * s[:, :, None, None] + res
+                return Fn.relu(v) if relu else v
+            y, yt = ours_fwd(), t_fwd()
+
+            def ours_bwd():
+                return torch.autograd.grad(y, [u, r] + ps, dy,
+                                           retain_graph=True)
+
+            def t_bwd():
+                return torch.autograd.grad(yt, [u, r] + wt, dy,
+                                           retain_graph=True)
+            # fp32 formula over the bf16-rounded operands, without its relu:
+            # the backward takes dy where OUR output is positive (borderline
+            # relu bits differ between any two roundings of the gate)
+            uf, rf = u.detach().float().requires_grad_(True), r.detach().float()
+            wf = [w.detach().float().requires_grad_(True) for w in wt]
+            v = t_fwd(uf, rf, wf, relu=False)
+            ge = dy.float() * (y > 0)
+            refs = torch.autograd.grad(v, [uf] + wf, ge)
+            got = ours_bwd()
+            checks = [("y", y.float(), v.detach().clamp_min(0)), ("dx", got[0].float(), refs[0]),
+                      ("dresid", got[1].float(), ge)]
+            checks += [(f"dparam{i}", got[2 + i].flatten(1).float()
+                        if got[2 + i].dim() == 4 else got[2 + i].float(),
+                        refs[1 + i]) for i in range(4)]
+            for name, a, b in checks:
+                # a bf16 ulp of the element plus 2^-6 of the largest: the
+                # gate's bf16 roundings at z, h, a reach every output
+                tol = 2.0 ** -7 * b.abs() + 2.0 ** -6 * b.abs().max()
+                if not bool(((a - b).abs() <= tol).all()):
+                    raise RuntimeError(
+                        f"se {name} B{N} C{C} H{H} differs from the fp32 "
+                        f"reference: largest error {(a - b).abs().max():.3g} "
+                        f"of largest value {b.abs().max():.3g}")
+            del uf, rf, wf, v, ge, refs, got, checks
+            ub = u.numel() * 2
+            for name, ours, theirs, traffic in (
+                    ("fwd", ours_fwd, t_fwd, 4 * ub),
+                    ("bwd", ours_bwd, t_bwd, 6 * ub)):
+                res = _time_alternating({"ours": ours, "torch": theirs},
+                                        rounds=rounds, warmup=30)
+                med, lo, hi = res["ours"]
+                tm = res["torch"][0]
+                print(f"{N:4d} {C:5d} {H:4d} {name:4s} {med:8.1f} {lo:8.1f} "
+                      f"{hi:8.1f} {traffic / HBM_PEAK * 1e6 / med * 100:6.1f} "
+                      f"{tm:9.1f} {tm / med:10.2f} {ub / 2 ** 20:7.1f}",
+                      flush=True)
+            del u, r, dy, y, yt, se, ps, wt
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--se", action="store_true")
     ap.add_argument("--gn", action="store_true")
     ap.add_argument("--gconv", action="store_true")
     ap.add_argument("--dwconv", action="store_true")
@@ -1004,6 +1105,9 @@ def main():
     ap.add_argument("--bnpool", action="store_true")
     ap.add_argument("--reps", type=int, default=200)
     args = ap.parse_args()
+    if args.se:
+        bench_se(rounds=30)
+        return
     if args.gn:
         bench_gn(rounds=30)
         return
