@@ -1,3 +1,4 @@
+from .mnasnet import mnasnet1_0  # noqa: F401
 from .mobilenet import mobilenet_v1  # noqa: F401
 from .resnet import (  # noqa: F401
     resnet18, resnet34, resnet50, resnext50_32x4d, resnext101_32x8d,
@@ -17,6 +18,7 @@ _REGISTRY = {
     "se_resnext50_32x4d": se_resnext50_32x4d,
     "vgg16": vgg16_bn,
     "mobilenet_v1": mobilenet_v1,
+    "mnasnet1_0": mnasnet1_0,
 }
 
 

@@ -29,6 +29,7 @@ SOURCES = [
     "gemm.hip",
     "conv.hip",
     "dwconv.hip",
+    "dwconvk.hip",
     "gconv.hip",
     "gn.hip",
     "se.hip",

@@ -366,9 +366,13 @@ def _uniform(v, name):
 
 # ------------------------------------------------------- depthwise conv2d ---
 
-DW_SCOPE = ("groups == C_in == C_out (channel multiplier 1) with a 3x3 "
-            "kernel, dilation 1, one stride of 1 or 2 and one padding of 0 "
-            "or 1 for both dims, C % 8 == 0 and an fp32 weight")
+DW_SCOPE = ("groups == C_in == C_out (channel multiplier 1), dilation 1, "
+            "C % 8 == 0, an fp32 weight and, with one stride and one padding "
+            "for both dims, a 3x3 kernel (stride 1 or 2, padding 0 or 1), a "
+            "5x5 kernel (stride 1 or 2, padding 0..2) or a 7x7 kernel "
+            "(stride 1, padding 0..3; 5x5 and 7x7 on a padded input no "
+            "smaller than the kernel)")
+_DWK_KS = ((5, 1), (5, 2), (7, 1))
 
 
 def _dw_in_scope(x, weight, stride, padding, groups, dilation) -> bool:
@@ -416,6 +420,83 @@ def _dw_bwd(ctx, dy):
     if want_db and not fuse_db:
         db = ext.col_sum(_nhwc_2d(dyb))
     return dx, dw, db
+
+
+def _dwk_in_scope(x, weight, stride, padding, groups, dilation) -> bool:
+    """Whether the depthwise 5x5 / 7x7 HIP kernels (hip/dwconvk.hip) serve
+    this conv."""
+    C, K = x.shape[1], weight.shape[-1]
+    return (groups == C and dilation == 1
+            and tuple(weight.shape) == (C, 1, K, K)
+            and weight.dtype == torch.float32 and C % 8 == 0
+            and (K, stride) in _DWK_KS and 0 <= padding <= K // 2
+            and min(x.shape[2], x.shape[3]) + 2 * padding >= K)
+
+
+def _dwk_fwd(ctx, x, weight, bias, stride, padding, want_stats):
+    """_dw_fwd on the KxK kernels: the bf16 x and the fp32 master weight."""
+    ext = require_ext_for(x)
+    xb = _chlast(_to_bf16(x))
+    y, stats = ext.dwconvk2d_fwd(
+        xb, weight.detach().contiguous(),
+        bias if bias is None else bias.detach().float().contiguous(),
+        stride, padding, want_stats)
+    ctx.save_for_backward(xb, weight)
+    ctx.meta = (stride, padding, x.dtype, bias is not None)
+    return y, stats
+
+
+def _dwk_bwd(ctx, dy):
+    xb, weight = ctx.saved_tensors
+    stride, padding, x_dtype, has_bias = ctx.meta
+    ext = require_ext_for(dy)
+    dyb = _chlast(_to_bf16(dy))
+    dx = dw = db = None
+    if ctx.needs_input_grad[0]:
+        dx = ext.dwconvk2d_dgrad(dyb, weight.detach().contiguous(),
+                                 xb.shape[2], xb.shape[3], stride, padding)
+        if x_dtype == torch.float32:
+            dx = dx.float()
+    want_db = has_bias and ctx.needs_input_grad[2]
+    # as _dw_bwd: the bias sums ride in the wgrad kernel when both are wanted
+    fuse_db = want_db and ctx.needs_input_grad[1]
+    if ctx.needs_input_grad[1]:
+        dw, dbf = ext.dwconvk2d_wgrad(dyb, xb, weight.shape[-1], stride,
+                                      padding, fuse_db)
+        if fuse_db:
+            db = dbf
+    if want_db and not fuse_db:
+        db = ext.col_sum(_nhwc_2d(dyb))
+    return dx, dw, db
+
+
+class _HIPDWKConv2d(torch.autograd.Function):
+    """Depthwise 5x5 / 7x7 conv on the LDS-tile kernels (see _dwk_in_scope)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, padding):
+        return _dwk_fwd(ctx, x, weight, bias, stride, padding, False)[0]
+
+    @staticmethod
+    def backward(ctx, dy):
+        dx, dw, db = _dwk_bwd(ctx, dy)
+        return dx, dw, db, None, None
+
+
+class _HIPDWKConv2dStats(torch.autograd.Function):
+    """_HIPDWKConv2d that also emits the consuming BN's partial statistics
+    (non-differentiable), like _HIPConv2dStats."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, padding):
+        y, stats = _dwk_fwd(ctx, x, weight, bias, stride, padding, True)
+        ctx.mark_non_differentiable(stats)
+        return y, stats
+
+    @staticmethod
+    def backward(ctx, dy, dstats):
+        dx, dw, db = _dwk_bwd(ctx, dy)
+        return dx, dw, db, None, None
 
 
 class _HIPDWConv2d(torch.autograd.Function):
@@ -533,13 +614,16 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, groups=1, dilation=1):
         if groups != 1 or dilation != 1:
             if _dw_in_scope(x, weight, stride, padding, groups, dilation):
                 return _HIPDWConv2d.apply(x, weight, bias, stride, padding)
+            if _dwk_in_scope(x, weight, stride, padding, groups, dilation):
+                return _HIPDWKConv2d.apply(x, weight, bias, stride, padding)
             if _g_in_scope(x, weight, stride, padding, groups, dilation):
                 return _HIPGConv2d.apply(x, weight, bias, stride, padding,
                                          groups)
             raise ValueError(
                 f"HIP conv2d: groups={groups}, dilation={dilation} with "
                 f"weight {tuple(weight.shape)}, stride={stride}, "
-                f"padding={padding} is not supported; besides dense convs "
+                f"padding={padding} on input {tuple(x.shape)} is not "
+                f"supported; besides dense convs "
                 f"(groups=1, dilation=1) the kernels serve depthwise convs: "
                 f"{DW_SCOPE}; and grouped convs: {G_SCOPE}")
         # NOTE: a 1x1-as-GEMM route through the linear kernels was tried and
@@ -1703,14 +1787,16 @@ def conv_bn(conv_mod, bn_mod, x, residual=None, pool=None):
                                                  (1, 1)) in ((1, 1), 1))
     stats = None
     groups = getattr(conv_mod, "groups", 1)
-    grouped = False
+    grouped = dwk = False
     if use_stats and groups != 1:
         # a depthwise or grouped conv in its kernels' scope emits the slab
         # too; any other goes through conv_mod and is refused there
         scope = (x, conv_mod.weight, _uniform(conv_mod.stride, "stride"),
                  _uniform(conv_mod.padding, "padding"), groups, 1)
-        grouped = not _dw_in_scope(*scope) and _g_in_scope(*scope)
-        use_stats = grouped or _dw_in_scope(*scope)
+        dwk = _dwk_in_scope(*scope)
+        depthwise = dwk or _dw_in_scope(*scope)
+        grouped = not depthwise and _g_in_scope(*scope)
+        use_stats = grouped or depthwise
     if use_stats:
         stride = _uniform(conv_mod.stride, "stride")
         padding = _uniform(conv_mod.padding, "padding")
@@ -1719,7 +1805,8 @@ def conv_bn(conv_mod, bn_mod, x, residual=None, pool=None):
                                               conv_mod.bias, stride, padding,
                                               groups)
         else:
-            fn = _HIPConv2dStats if groups == 1 else _HIPDWConv2dStats
+            fn = (_HIPConv2dStats if groups == 1 else
+                  _HIPDWKConv2dStats if dwk else _HIPDWConv2dStats)
             y, stats = fn.apply(x, conv_mod.weight, conv_mod.bias, stride,
                                 padding)
     else:

@@ -191,6 +191,21 @@ std::tuple<long, long, long, long> dwconv2d_plan(std::string op, long N,
                                                  long stride, long pad,
                                                  long tr);
 
+// dwconvk.hip
+std::tuple<at::Tensor, at::Tensor> dwconvk2d_fwd(
+    at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias, long stride,
+    long pad, bool want_stats, long to);
+at::Tensor dwconvk2d_dgrad(at::Tensor dy, at::Tensor w, long H, long W,
+                           long stride, long pad, long to);
+std::tuple<at::Tensor, at::Tensor> dwconvk2d_wgrad(at::Tensor dy, at::Tensor x,
+                                                   long K, long stride,
+                                                   long pad, bool want_db,
+                                                   long to);
+std::tuple<long, long, long, long> dwconvk2d_plan(std::string op, long N,
+                                                  long C, long H, long W,
+                                                  long K, long stride,
+                                                  long pad, long to);
+
 // gconv.hip
 std::tuple<at::Tensor, at::Tensor> gconv2d_pack(at::Tensor w);
 std::tuple<at::Tensor, at::Tensor> gconv2d_fwd(
@@ -461,6 +476,31 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("op"), py::arg("N"), py::arg("C"), py::arg("H"),
           py::arg("W"), py::arg("stride"), py::arg("pad"),
           py::arg("tr") = -1);
+    m.def("dwconvk2d_fwd", &dwconvk2d_fwd,
+          "depthwise 5x5 / 7x7 forward from bf16 channels_last x and the fp32 "
+          "master weight [C,1,K,K]: (y, slab); slab is the [2, C, S] BN "
+          "partial slab with want_stats, else undefined",
+          py::arg("x"), py::arg("w"), py::arg("bias") = c10::nullopt,
+          py::arg("stride") = 1, py::arg("pad") = 0,
+          py::arg("want_stats") = false, py::arg("to") = -1);
+    m.def("dwconvk2d_dgrad", &dwconvk2d_dgrad,
+          "depthwise 5x5 / 7x7 backward-data: dx bf16 [N,C,H,W], every "
+          "element written",
+          py::arg("dy"), py::arg("w"), py::arg("H"), py::arg("W"),
+          py::arg("stride") = 1, py::arg("pad") = 0, py::arg("to") = -1);
+    m.def("dwconvk2d_wgrad", &dwconvk2d_wgrad,
+          "depthwise 5x5 / 7x7 backward-weight: (dw fp32 [C,1,K,K], db fp32 "
+          "[C] or undefined)",
+          py::arg("dy"), py::arg("x"), py::arg("K"), py::arg("stride") = 1,
+          py::arg("pad") = 0, py::arg("want_db") = false,
+          py::arg("to") = -1);
+    m.def("dwconvk2d_plan", &dwconvk2d_plan,
+          "(slice width in chunks, rows per run / group, grid x, grid y) of "
+          "the depthwise KxK kernel for op 'fwd', 'dgrad' or 'wgrad' over an "
+          "[N,C,H,W] input; launches nothing",
+          py::arg("op"), py::arg("N"), py::arg("C"), py::arg("H"),
+          py::arg("W"), py::arg("K"), py::arg("stride"), py::arg("pad"),
+          py::arg("to") = -1);
     m.def("gconv2d_pack", &gconv2d_pack,
           "grouped 3x3 weight pack: fp32 master [C,Cg,3,3] -> (forward image, "
           "dgrad image), each bf16 [C/64, 9, 64, 64]",

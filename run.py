@@ -43,7 +43,8 @@ def parse_args():
                         help="model registry name (toy_net, vgg16, resnet18, "
                              "resnet34, resnet50, resnext50_32x4d, "
                              "resnext101_32x8d, se_resnet50, "
-                             "se_resnext50_32x4d, mobilenet_v1)")
+                             "se_resnext50_32x4d, mobilenet_v1, "
+                             "mnasnet1_0)")
     parser.add_argument("--dataset", default="mnist", type=str,
                         help="dataset registry name (mnist, cifar10, "
                              "imagenet_synthetic)")

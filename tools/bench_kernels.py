@@ -11,6 +11,7 @@ Usage (on a GPU box):  python tools/bench_kernels.py [--resnet]
                        python tools/bench_kernels.py --stem
                        python tools/bench_kernels.py --linear
                        python tools/bench_kernels.py --dwconv [--trs 4,8,32]
+                       python tools/bench_kernels.py --dwconvk [--tos 1,2,4]
                        python tools/bench_kernels.py --gconv
                        python tools/bench_kernels.py --gn | --se
 
@@ -769,6 +770,88 @@ def bench_dwconv(rounds, trs):
         torch.cuda.empty_cache()
 
 
+# (K, C, H, stride): MnasNet-B1's six 5x5 depthwise shapes, then 7x7 stride 1
+DWCONVK = [(5, 72, 56, 2), (5, 120, 28, 1), (5, 240, 28, 2), (5, 480, 14, 1),
+           (5, 576, 14, 2), (5, 1152, 7, 1),
+           (7, 96, 56, 1), (7, 192, 28, 1), (7, 384, 14, 1), (7, 768, 7, 1)]
+
+
+def bench_dwconvk(rounds, tos):
+    """Depthwise 5x5 / 7x7 kernels (dwconvk.hip) at B = 256, pad K // 2,
+    against torch's own kernels for F.conv2d(groups=C) in bf16 channels_last
+    (aten convolution / convolution_backward with one output mask bit each),
+    alternated in one process: 30 warm-up calls, device events around 10
+    calls, median of `rounds` rounds with min-max.  %HBM is the time the op's
+    two activation tensors take once each at 8 TB/s (x + y forward, dy + dx
+    dgrad, dy + x wgrad) as a share of the measured time.  Outputs are
+    compared with torch's before timing.  `tos`: further run heights timed
+    for the forward (the plan's choice is -1)."""
+    ext = load_extension(required=True)
+    dev = torch.device("cuda:0")
+    N = 256
+    aten = torch.ops.aten
+    print(f"{'K':>2s} {'C':>5s} {'H':>4s} {'s':>2s} {'op':10s} {'med us':>8s} "
+          f"{'min':>8s} {'max':>8s} {'GB/s':>7s} {'%HBM':>6s} "
+          f"{'torch us':>9s} {'torch/ours':>10s}")
+    for K, C, H, stride in DWCONVK:
+        pad = K // 2
+        g = torch.Generator(device=dev).manual_seed(K + C + H + stride)
+        P = (H + 2 * pad - K) // stride + 1
+        x = torch.randn(N, C, H, H, device=dev, generator=g) \
+            .to(torch.bfloat16).contiguous(memory_format=CL)
+        dy = torch.randn(N, C, P, P, device=dev, generator=g) \
+            .to(torch.bfloat16).contiguous(memory_format=CL)
+        w = torch.randn(C, 1, K, K, device=dev, generator=g) / K
+        wb = w.to(torch.bfloat16).contiguous(memory_format=CL)
+        nbytes = (x.numel() + dy.numel()) * 2
+
+        def t_bwd(mask):
+            return aten.convolution_backward(
+                dy, x, wb, None, [stride] * 2, [pad] * 2, [1, 1], False,
+                [0, 0], C, mask)
+        ops = {
+            "fwd": (lambda to=-1: ext.dwconvk2d_fwd(x, w, None, stride, pad,
+                                                    False, to)[0],
+                    lambda: torch.nn.functional.conv2d(
+                        x, wb, None, stride, pad, 1, C)),
+            "fwd+stats": (lambda: ext.dwconvk2d_fwd(x, w, None, stride, pad,
+                                                    True)[0], None),
+            "dgrad": (lambda: ext.dwconvk2d_dgrad(dy, w, H, H, stride, pad),
+                      lambda: t_bwd([True, False, False])[0]),
+            "wgrad": (lambda: ext.dwconvk2d_wgrad(dy, x, K, stride, pad,
+                                                  False)[0],
+                      lambda: t_bwd([False, True, False])[1].float()),
+        }
+        for name, (ours, theirs) in ops.items():
+            variants = {"ours": ours}
+            if theirs is not None:
+                a, b = ours().float(), theirs().float()
+                err = float((a - b).abs().max() / b.abs().max())
+                # torch's results are bf16 (its wgrad too): one bf16 ulp of
+                # the largest element is 2^-7 of it
+                if err > 2.0 ** -5:
+                    raise RuntimeError(f"dwconvk {name} K{K} C{C} H{H} "
+                                       f"s{stride}: differs from torch by "
+                                       f"{err:.3g}")
+                variants["torch"] = theirs
+            if name == "fwd":
+                for to in tos:
+                    variants[f"to{to}"] = (lambda to=to: ours(to))
+            res = _time_alternating(variants, rounds=rounds, warmup=30)
+            med, lo, hi = res["ours"]
+            tm = res["torch"][0] if "torch" in res else float("nan")
+            print(f"{K:2d} {C:5d} {H:4d} {stride:2d} {name:10s} {med:8.1f} "
+                  f"{lo:8.1f} {hi:8.1f} {nbytes / med / 1e3:7.0f} "
+                  f"{nbytes / HBM_PEAK * 1e6 / med * 100:6.1f} {tm:9.1f} "
+                  f"{tm / med:10.2f}", flush=True)
+            for to in (tos if name == "fwd" else ()):
+                m2 = res[f"to{to}"]
+                print(f"{'':15s} fwd to={to:<3d} {m2[0]:8.1f} {m2[1]:8.1f} "
+                      f"{m2[2]:8.1f}", flush=True)
+        del x, dy
+        torch.cuda.empty_cache()
+
+
 # ResNeXt-50 32x4d's grouped convs (C, H, stride, Cg) and a Cg = 64 layer
 GCONV = [(128, 56, 1, 4), (256, 56, 2, 8), (256, 28, 1, 8), (512, 28, 2, 16),
          (512, 14, 1, 16), (1024, 14, 2, 32), (1024, 7, 1, 32),
@@ -1083,6 +1166,10 @@ def main():
     ap.add_argument("--trs", default="",
                     help="further forward strip heights for --dwconv, comma "
                          "separated (e.g. 4,8,32)")
+    ap.add_argument("--dwconvk", action="store_true")
+    ap.add_argument("--tos", default="",
+                    help="further forward run heights for --dwconvk, comma "
+                         "separated")
     ap.add_argument("--clip", action="store_true")
     ap.add_argument("--wgradbias", action="store_true")
     ap.add_argument("--wgraddma", action="store_true")
@@ -1113,6 +1200,10 @@ def main():
         return
     if args.gconv:
         bench_gconv(rounds=30)
+        return
+    if args.dwconvk:
+        bench_dwconvk(rounds=30,
+                      tos=[int(v) for v in args.tos.split(",") if v])
         return
     if args.dwconv:
         bench_dwconv(rounds=30,
