@@ -1,3 +1,4 @@
+from .convnext import convnext_tiny  # noqa: F401
 from .mnasnet import mnasnet1_0  # noqa: F401
 from .mobilenet import mobilenet_v1  # noqa: F401
 from .resnet import (  # noqa: F401
@@ -19,6 +20,7 @@ _REGISTRY = {
     "vgg16": vgg16_bn,
     "mobilenet_v1": mobilenet_v1,
     "mnasnet1_0": mnasnet1_0,
+    "convnext_tiny": convnext_tiny,
 }
 
 

@@ -33,6 +33,7 @@ SOURCES = [
     "gconv.hip",
     "gn.hip",
     "se.hip",
+    "ln.hip",
     "data.hip",
 ]
 

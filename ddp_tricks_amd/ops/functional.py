@@ -1209,6 +1209,127 @@ def se_scale(u, fc1_weight, fc1_bias, fc2_weight, fc2_bias, residual=None,
     return y.to(u.dtype) if u.is_cuda and amp_mod.is_enabled() else y
 
 
+# ------------------------------------- layer norm, gelu, layer scale (ln.hip) ---
+
+LN_MAX_C = 2048
+LN_SCOPE = ("4-D [N, C, H, W] input with C % 8 == 0 and C <= "
+            f"{LN_MAX_C} (bf16 channels_last; other dtypes and layouts are "
+            "converted)")
+
+
+def _ln_check_scope(x, who: str) -> None:
+    if x.dim() != 4 or x.shape[1] % 8 != 0 or x.shape[1] > LN_MAX_C:
+        raise ValueError(f"HIP {who}: input {tuple(x.shape)} is not "
+                         f"supported; the kernels serve {LN_SCOPE}")
+
+
+class _HIPLayerNorm2d(torch.autograd.Function):
+    """LayerNorm over the channels of every pixel of a 4-D channels_last bf16
+    activation (ops/hip/ln.hip): one pass forward, one pass plus the slab
+    combine backward.  mean / rstd are saved only when a backward will run."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps):
+        ext = require_ext_for(x)
+        xb = _chlast(_to_bf16(x))
+        save = any(ctx.needs_input_grad)
+        y, mean, rstd = ext.ln2d_fwd(xb, weight.detach().float(),
+                                     bias.detach().float(), eps, save)
+        ctx.save_for_backward(xb, weight, mean, rstd)
+        ctx.x_dtype = x.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xb, weight, mean, rstd = ctx.saved_tensors
+        ext = require_ext_for(dy)
+        dx, dweight, dbias = ext.ln2d_bwd(xb, _chlast(_to_bf16(dy)),
+                                          weight.detach().float(), mean, rstd)
+        if ctx.x_dtype == torch.float32:
+            dx = dx.float()
+        return dx, dweight.to(weight.dtype), dbias.to(weight.dtype), None
+
+
+def layer_norm2d(x, weight, bias, eps=1e-6):
+    """LayerNorm over dim 1 of [N, C, H, W] (per pixel, over its channels) with
+    affine weight / bias [C] — ConvNeXt's ``LayerNorm2d``."""
+    if x.is_cuda and require_ext_for(x) is not None:
+        _ln_check_scope(x, "layer_norm2d")
+        return _HIPLayerNorm2d.apply(x, weight, bias, eps)
+    xf = x.float() if x.dtype not in (torch.float32, torch.float64) else x
+    y = F.layer_norm(xf.permute(0, 2, 3, 1), (x.shape[1],), weight.to(xf.dtype),
+                     bias.to(xf.dtype), eps).permute(0, 3, 1, 2)
+    return y.to(x.dtype) if x.is_cuda and amp_mod.is_enabled() else y
+
+
+class _HIPGelu(torch.autograd.Function):
+    """Exact (erf) GELU; the saved tensor is the pre-activation."""
+
+    @staticmethod
+    def forward(ctx, z):
+        ext = require_ext_for(z)
+        zb = _chlast(_to_bf16(z))
+        ctx.save_for_backward(zb)
+        ctx.z_dtype = z.dtype
+        return ext.gelu_fwd(zb)
+
+    @staticmethod
+    def backward(ctx, dy):
+        zb, = ctx.saved_tensors
+        ext = require_ext_for(dy)
+        dz = ext.gelu_bwd(_chlast(_to_bf16(dy)), zb)
+        return dz.float() if ctx.z_dtype == torch.float32 else dz
+
+
+def gelu(x):
+    """x/2 (1 + erf(x / sqrt 2)), elementwise."""
+    if x.is_cuda and require_ext_for(x) is not None:
+        if x.numel() % 8 != 0 or x.numel() == 0:
+            raise ValueError(f"HIP gelu: input {tuple(x.shape)} is not "
+                             "supported; the kernel serves tensors with "
+                             "numel % 8 == 0")
+        return _HIPGelu.apply(x)
+    return F.gelu(x)
+
+
+class _HIPLayerScale(torch.autograd.Function):
+    """residual + gamma[c] * u over 4-D channels_last bf16 activations; the
+    residual's gradient is the incoming gradient itself, not a copy."""
+
+    @staticmethod
+    def forward(ctx, u, gamma, residual):
+        ext = require_ext_for(u)
+        ub = _chlast(_to_bf16(u))
+        ctx.save_for_backward(ub, gamma)
+        ctx.dtypes = (u.dtype, residual.dtype)
+        return ext.lscale_fwd(ub, gamma.detach().float(),
+                              _chlast(_to_bf16(residual)))
+
+    @staticmethod
+    def backward(ctx, dy):
+        ub, gamma = ctx.saved_tensors
+        ext = require_ext_for(dy)
+        dyb = _chlast(_to_bf16(dy))
+        du, dgamma = ext.lscale_bwd(dyb, ub, gamma.detach().float())
+        u_dtype, r_dtype = ctx.dtypes
+        if u_dtype == torch.float32:
+            du = du.float()
+        dres = dyb.float() if r_dtype == torch.float32 else dyb
+        return du, dgamma.to(gamma.dtype), dres
+
+
+def layer_scale(u, gamma, residual):
+    """residual + gamma.view(1, C, 1, 1) * u — ConvNeXt's layer scale with the
+    block's residual add."""
+    if u.is_cuda and require_ext_for(u) is not None:
+        _ln_check_scope(u, "layer_scale")
+        if residual.shape != u.shape:
+            raise ValueError(f"HIP layer_scale: residual {tuple(residual.shape)}"
+                             f" differs from u {tuple(u.shape)}")
+        return _HIPLayerScale.apply(u, gamma, residual)
+    return residual + gamma.view(1, -1, 1, 1).to(u.dtype) * u
+
+
 # -------------------------------------------------------- sync batch norm ---
 
 def _gather_rows(row, group, native):

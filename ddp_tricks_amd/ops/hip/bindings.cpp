@@ -244,6 +244,20 @@ std::tuple<at::Tensor, c10::optional<at::Tensor>> se_bwd_dx(
 std::tuple<long, long, long, long> se_plan(long N, long C, long H, long W,
                                            long strips);
 
+// ln.hip
+std::tuple<at::Tensor, at::Tensor, at::Tensor> ln2d_fwd(
+    at::Tensor x, at::Tensor gamma, at::Tensor beta, double eps, bool save,
+    long blocks);
+std::tuple<at::Tensor, at::Tensor, at::Tensor> ln2d_bwd(
+    at::Tensor x, at::Tensor dy, at::Tensor gamma, at::Tensor mean,
+    at::Tensor rstd, long blocks);
+std::tuple<long, long, long, long> ln2d_plan(long M, long C, long blocks);
+at::Tensor gelu_fwd(at::Tensor z);
+at::Tensor gelu_bwd(at::Tensor dy, at::Tensor z);
+at::Tensor lscale_fwd(at::Tensor u, at::Tensor gamma, at::Tensor resid);
+std::tuple<at::Tensor, at::Tensor> lscale_bwd(at::Tensor dy, at::Tensor u,
+                                              at::Tensor gamma, long blocks);
+
 // data.hip
 std::vector<at::Tensor> batch_gather_aug(at::Tensor store, at::Tensor labels,
                                          at::Tensor index, at::Tensor lut,
@@ -576,6 +590,35 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "count, clamped to H*W; launches nothing",
           py::arg("N"), py::arg("C"), py::arg("H"), py::arg("W"),
           py::arg("strips") = -1);
+    m.def("ln2d_fwd", &ln2d_fwd,
+          "LayerNorm over the C channels of every pixel of bf16 channels_last "
+          "x (C % 8 == 0, C <= 2048): (y, mean [N*H*W], rstd [N*H*W]); the "
+          "statistics are written only with save; blocks > 0 forces the grid",
+          py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("eps"),
+          py::arg("save"), py::arg("blocks") = -1);
+    m.def("ln2d_bwd", &ln2d_bwd,
+          "LayerNorm backward: (dx, dgamma, dbeta)",
+          py::arg("x"), py::arg("dy"), py::arg("gamma"), py::arg("mean"),
+          py::arg("rstd"), py::arg("blocks") = -1);
+    m.def("ln2d_plan", &ln2d_plan,
+          "(lanes per row, chunks per lane, rows per group, backward grid) of "
+          "the LayerNorm / layer-scale kernels over M rows of C channels; "
+          "blocks > 0 forces the grid, clamped to the number of row groups; "
+          "launches nothing",
+          py::arg("M"), py::arg("C"), py::arg("blocks") = -1);
+    m.def("gelu_fwd", &gelu_fwd,
+          "a = z/2 (1 + erf(z / sqrt 2)) over a dense bf16 tensor, "
+          "numel % 8 == 0", py::arg("z"));
+    m.def("gelu_bwd", &gelu_bwd,
+          "dz = dy (Phi(z) + z phi(z)) for the pre-activation z",
+          py::arg("dy"), py::arg("z"));
+    m.def("lscale_fwd", &lscale_fwd,
+          "y = resid + gamma[c] * u over bf16 channels_last tensors",
+          py::arg("u"), py::arg("gamma"), py::arg("resid"));
+    m.def("lscale_bwd", &lscale_bwd,
+          "(du, dgamma) of the layer scale; the residual's gradient is dy",
+          py::arg("dy"), py::arg("u"), py::arg("gamma"),
+          py::arg("blocks") = -1);
     m.def("conv2d_kloop_plan", &conv2d_kloop_plan,
           "'walk' or 'decode': the K loop conv2d_fwd[_stats] (mode 0) or "
           "conv2d_dgrad (mode 1) would run for this shape; kwalk -1 "

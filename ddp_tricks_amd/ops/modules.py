@@ -156,6 +156,40 @@ class SqueezeExcite(nn.Module):
                               residual=residual, fuse_relu=fuse_relu)
 
 
+class LayerNorm2d(nn.Module):
+    """LayerNorm over the channels of every pixel of an [N, C, H, W] tensor
+    (ConvNeXt's norm): parameters ``weight`` and ``bias`` of shape [C], on the
+    one-pass HIP kernels of ops/hip/ln.hip."""
+
+    def __init__(self, channels: int, eps: float = 1e-6):
+        super().__init__()
+        self.eps = eps
+        self.weight = nn.Parameter(torch.ones(channels))
+        self.bias = nn.Parameter(torch.zeros(channels))
+
+    def forward(self, x):
+        return F_ops.layer_norm2d(x, self.weight, self.bias, self.eps)
+
+
+class GELU(nn.Module):
+    """Exact (erf) GELU on the HIP kernel."""
+
+    def forward(self, x):
+        return F_ops.gelu(x)
+
+
+class LayerScale(nn.Module):
+    """``forward(u, residual)`` is residual + gamma[c] * u: ConvNeXt's
+    per-channel layer scale with the block's residual add in one kernel."""
+
+    def __init__(self, channels: int, init: float = 1e-6):
+        super().__init__()
+        self.gamma = nn.Parameter(torch.full((channels,), float(init)))
+
+    def forward(self, u, residual):
+        return F_ops.layer_scale(u, self.gamma, residual)
+
+
 class ReLU(nn.ReLU):
     def forward(self, x):
         return F_ops.relu(x, inplace=self.inplace)

@@ -14,6 +14,7 @@ Usage (on a GPU box):  python tools/bench_kernels.py [--resnet]
                        python tools/bench_kernels.py --dwconvk [--tos 1,2,4]
                        python tools/bench_kernels.py --gconv
                        python tools/bench_kernels.py --gn | --se
+                       python tools/bench_kernels.py --ln [--blocks 512,4096]
 
 Times conv fwd/dgrad/wgrad per shape with HIP events (200 reps after 20
 warmup) and prints achieved TFLOP/s next to microseconds, so kernel A/B
@@ -1157,8 +1158,131 @@ def bench_se(rounds):
             torch.cuda.empty_cache()
 
 
+# ConvNeXt-T stages (C, H) for --ln
+LN_SHAPES = [(96, 56), (192, 28), (384, 14), (768, 7)]
+
+
+def bench_ln(rounds, blocks):
+    """LayerNorm over C, GELU and layer scale (ln.hip) at B = 256 on
+    ConvNeXt-T's four stages, the bindings against torch on the same bf16
+    tensors: F.layer_norm over the permuted (NHWC-shaped) view and its
+    autograd, F.gelu on the 4C-wide tensor and its autograd, resid + gamma * u
+    and its autograd.  Alternated in one process, 30 warm-up calls, device
+    events around 10 calls.  Each row: median us (min-max), the share of the
+    HBM-bound time of the least traffic at 8 TB/s (activation tensors only:
+    ln fwd x + y, bwd x + dy + dx; gelu fwd 2, bwd 3 tensors; layer scale fwd
+    u + resid + y, bwd dy + u + du), torch's median and its ratio to ours.
+    `blocks` adds LayerNorm forward / backward rows at forced grids.  Outputs
+    are first compared with the fp32 formulas."""
+    ext = load_extension(required=True)
+    dev = torch.device("cuda:0")
+    Fn = torch.nn.functional
+    N = 256
+    print(f"{'C':>5s} {'H':>4s} {'op':12s} {'med us':>8s} {'min':>8s} "
+          f"{'max':>8s} {'%HBM':>6s} {'torch us':>9s} {'torch/ours':>10s} "
+          f"{'MiB':>7s}")
+
+    def check(name, a, b):
+        # a bf16 ulp of the element plus 2^-8 of the largest value
+        tol = 2.0 ** -7 * b.abs() + 2.0 ** -8 * b.abs().max()
+        if not bool(((a.float() - b).abs() <= tol).all()):
+            raise RuntimeError(f"ln {name} differs from the fp32 reference: "
+                               f"largest error {(a.float() - b).abs().max():.3g}")
+
+    def row(C, H, name, ours, theirs, traffic, nbytes):
+        res = _time_alternating({"ours": ours, "torch": theirs},
+                                rounds=rounds, warmup=30)
+        med, lo, hi = res["ours"]
+        tm = res["torch"][0]
+        print(f"{C:5d} {H:4d} {name:12s} {med:8.1f} {lo:8.1f} {hi:8.1f} "
+              f"{traffic / HBM_PEAK * 1e6 / med * 100:6.1f} {tm:9.1f} "
+              f"{tm / med:10.2f} {nbytes / 2 ** 20:7.1f}", flush=True)
+
+    for C, H in LN_SHAPES:
+        g = torch.Generator(device=dev).manual_seed(C + H)
+
+        def act(c):
+            return (torch.randn(N, c, H, H, device=dev, generator=g)
+                    .to(torch.bfloat16).contiguous(memory_format=CL))
+        x, r, dy = act(C), act(C), act(C)
+        w = 1 + 0.5 * torch.randn(C, device=dev, generator=g)
+        b = 0.5 * torch.randn(C, device=dev, generator=g)
+        wb, bb = (t.bfloat16().requires_grad_(True) for t in (w, b))
+        nb = x.numel() * 2
+
+        # ---- LayerNorm
+        xt = x.permute(0, 2, 3, 1).requires_grad_(True)
+        dyt = dy.permute(0, 2, 3, 1)
+        yt = Fn.layer_norm(xt, (C,), wb, bb, 1e-6)
+        y, mean, rstd = ext.ln2d_fwd(x, w, b, 1e-6, True)
+        xf = xt.detach().float().requires_grad_(True)
+        wf, bf = (t.clone().requires_grad_(True) for t in (w, b))
+        yf = Fn.layer_norm(xf, (C,), wf, bf, 1e-6)
+        refs = torch.autograd.grad(yf, [xf, wf, bf], dyt.float())
+        got = ext.ln2d_bwd(x, dy, w, mean, rstd)
+        check("y", y.permute(0, 2, 3, 1), yf.detach())
+        check("dx", got[0].permute(0, 2, 3, 1), refs[0])
+        check("dgamma", got[1], refs[1])
+        check("dbeta", got[2], refs[2])
+        del xf, yf, refs, got
+        row(C, H, "ln fwd", lambda: ext.ln2d_fwd(x, w, b, 1e-6, True),
+            lambda: Fn.layer_norm(xt, (C,), wb, bb, 1e-6), 2 * nb, nb)
+        row(C, H, "ln bwd", lambda: ext.ln2d_bwd(x, dy, w, mean, rstd),
+            lambda: torch.autograd.grad(yt, [xt, wb, bb], dyt,
+                                        retain_graph=True), 3 * nb, nb)
+        for k in blocks:
+            row(C, H, f"ln fwd b{k}",
+                lambda: ext.ln2d_fwd(x, w, b, 1e-6, True, k),
+                lambda: Fn.layer_norm(xt, (C,), wb, bb, 1e-6), 2 * nb, nb)
+            row(C, H, f"ln bwd b{k}",
+                lambda: ext.ln2d_bwd(x, dy, w, mean, rstd, k),
+                lambda: torch.autograd.grad(yt, [xt, wb, bb], dyt,
+                                            retain_graph=True), 3 * nb, nb)
+        del xt, yt, y, mean, rstd
+
+        # ---- layer scale
+        ut, rt = x.detach().requires_grad_(True), r.detach().requires_grad_(True)
+        st = wb.view(1, -1, 1, 1) * ut + rt
+        uf, rf = x.float().requires_grad_(True), r.float().requires_grad_(True)
+        sf = wf.view(1, -1, 1, 1) * uf + rf
+        refs = torch.autograd.grad(sf, [uf, wf], dy.float())
+        du, dgam = ext.lscale_bwd(dy, x, w)
+        check("lscale y", ext.lscale_fwd(x, w, r), sf.detach())
+        check("lscale du", du, refs[0])
+        check("lscale dgamma", dgam, refs[1])
+        del uf, rf, sf, refs, du, dgam
+        row(C, H, "lscale fwd", lambda: ext.lscale_fwd(x, w, r),
+            lambda: wb.view(1, -1, 1, 1) * ut + rt, 3 * nb, nb)
+        row(C, H, "lscale bwd", lambda: ext.lscale_bwd(dy, x, w),
+            lambda: torch.autograd.grad(st, [ut, rt, wb], dy,
+                                        retain_graph=True), 3 * nb, nb)
+        del ut, rt, st, x, r, dy
+
+        # ---- GELU on the 4C-wide hidden tensor
+        z, dz = act(4 * C), act(4 * C)
+        zt = z.detach().requires_grad_(True)
+        at_ = Fn.gelu(zt)
+        zf = z.float().requires_grad_(True)
+        af = Fn.gelu(zf)
+        check("gelu a", ext.gelu_fwd(z), af.detach())
+        check("gelu dz", ext.gelu_bwd(dz, z),
+              torch.autograd.grad(af, zf, dz.float())[0])
+        del zf, af
+        row(4 * C, H, "gelu fwd", lambda: ext.gelu_fwd(z),
+            lambda: Fn.gelu(zt), 2 * 4 * nb, 4 * nb)
+        row(4 * C, H, "gelu bwd", lambda: ext.gelu_bwd(dz, z),
+            lambda: torch.autograd.grad(at_, zt, dz, retain_graph=True),
+            3 * 4 * nb, 4 * nb)
+        del z, dz, zt, at_
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ln", action="store_true")
+    ap.add_argument("--blocks", default="",
+                    help="further forced grids for --ln's LayerNorm rows, "
+                         "comma separated (e.g. 512,4096)")
     ap.add_argument("--se", action="store_true")
     ap.add_argument("--gn", action="store_true")
     ap.add_argument("--gconv", action="store_true")
@@ -1192,6 +1316,10 @@ def main():
     ap.add_argument("--bnpool", action="store_true")
     ap.add_argument("--reps", type=int, default=200)
     args = ap.parse_args()
+    if args.ln:
+        bench_ln(rounds=30,
+                 blocks=[int(t) for t in args.blocks.split(",") if t])
+        return
     if args.se:
         bench_se(rounds=30)
         return
