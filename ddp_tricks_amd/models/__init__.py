@@ -7,6 +7,7 @@ from .resnet import (  # noqa: F401
 )
 from .toy_net import Toy_Net  # noqa: F401
 from .vgg import vgg16_bn  # noqa: F401
+from .vit import vit_small, vit_tiny  # noqa: F401
 
 _REGISTRY = {
     "toy_net": Toy_Net,
@@ -21,6 +22,8 @@ _REGISTRY = {
     "mobilenet_v1": mobilenet_v1,
     "mnasnet1_0": mnasnet1_0,
     "convnext_tiny": convnext_tiny,
+    "vit_tiny": vit_tiny,
+    "vit_small": vit_small,
 }
 
 

@@ -34,6 +34,7 @@ SOURCES = [
     "gn.hip",
     "se.hip",
     "ln.hip",
+    "attn.hip",
     "data.hip",
 ]
 

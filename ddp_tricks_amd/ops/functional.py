@@ -1330,6 +1330,97 @@ def layer_scale(u, gamma, residual):
     return residual + gamma.view(1, -1, 1, 1).to(u.dtype) * u
 
 
+# ------------------------------------------------- attention (attn.hip) ---
+
+ATTN_HEAD_DIM = 64
+ATTN_SCOPE = ("non-causal self-attention over a packed 4-D [N, 3 * 64 * heads,"
+              " H, W] qkv with head dimension 64 exactly (bf16 channels_last; "
+              "other dtypes and layouts are converted), no mask, no dropout")
+
+
+def _attn_heads_view(t, num_heads):
+    """[N, num_heads * 64, H, W] -> [N, num_heads, L, 64]."""
+    N, C, H, W = t.shape
+    return t.permute(0, 2, 3, 1).reshape(N, H * W, num_heads,
+                                         ATTN_HEAD_DIM).transpose(1, 2)
+
+
+def _attn_torch(qkv, num_heads):
+    N, _, H, W = qkv.shape
+    q, k, v = (_attn_heads_view(t, num_heads) for t in qkv.chunk(3, dim=1))
+    p = torch.softmax(q @ k.transpose(-1, -2) * 0.125, dim=-1)
+    return (p @ v).transpose(1, 2).reshape(N, H, W, -1).permute(0, 3, 1, 2)
+
+
+class _HIPAttention2d(torch.autograd.Function):
+    """softmax(q k^T / 8) v per head (ops/hip/attn.hip): a streaming-softmax
+    forward, and a backward of two kernels that recompute the scores from the
+    saved qkv, o and log-sum-exp.  lse is written only when a backward will
+    run."""
+
+    @staticmethod
+    def forward(ctx, qkv, num_heads):
+        ext = require_ext_for(qkv)
+        qb = _chlast(_to_bf16(qkv))
+        save = ctx.needs_input_grad[0]
+        o, lse = ext.attn_fwd(qb, num_heads, save)
+        ctx.save_for_backward(qb, o, lse)
+        ctx.num_heads = num_heads
+        ctx.x_dtype = qkv.dtype
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qb, o, lse = ctx.saved_tensors
+        ext = require_ext_for(do)
+        dqkv = ext.attn_bwd(qb, o, lse, _chlast(_to_bf16(do)), ctx.num_heads)
+        return (dqkv.float() if ctx.x_dtype == torch.float32 else dqkv), None
+
+
+def attention2d(qkv, num_heads):
+    """Multi-head self-attention over the H * W tokens of a packed qkv
+    activation [N, 3 D, H, W], D = 64 num_heads: channels [0, D) are q,
+    [D, 2D) k, [2D, 3D) v, head h at offset 64 h of each — the output of a
+    ``Conv2d(D, 3 * D, 1)``.  Returns [N, D, H, W]."""
+    if qkv.is_cuda and require_ext_for(qkv) is not None:
+        if qkv.dim() != 4 or qkv.shape[1] != 3 * ATTN_HEAD_DIM * num_heads:
+            raise ValueError(f"HIP attention2d: qkv {tuple(qkv.shape)} with "
+                             f"{num_heads} heads is not supported; the kernels "
+                             f"serve {ATTN_SCOPE}")
+        return _HIPAttention2d.apply(qkv, num_heads)
+    xf = qkv.float() if qkv.dtype not in (torch.float32, torch.float64) else qkv
+    y = _attn_torch(xf, num_heads)
+    return y.to(qkv.dtype) if qkv.is_cuda and amp_mod.is_enabled() else y
+
+
+class _HIPAddPos(torch.autograd.Function):
+    """x + pos for a fixed table pos [1, C, H, W]; the gradient passes through
+    untouched."""
+
+    @staticmethod
+    def forward(ctx, x, pos):
+        ext = require_ext_for(x)
+        ctx.x_dtype = x.dtype
+        return ext.add_pos_fwd(_chlast(_to_bf16(x)), _chlast(_to_bf16(pos)))
+
+    @staticmethod
+    def backward(ctx, dy):
+        return (dy.float() if ctx.x_dtype == torch.float32 else dy), None
+
+
+def add_pos(x, pos):
+    """x + pos with pos [1, C, H, W] broadcast over the batch; pos is a
+    buffer, not a parameter."""
+    if x.is_cuda and require_ext_for(x) is not None:
+        if (x.dim() != 4 or x.shape[1] % 8 != 0
+                or tuple(pos.shape) != (1,) + tuple(x.shape[1:])):
+            raise ValueError(f"HIP add_pos: x {tuple(x.shape)} with pos "
+                             f"{tuple(pos.shape)} is not supported; the kernel "
+                             "serves 4-D x with C % 8 == 0 and pos [1, C, H, W]")
+        return _HIPAddPos.apply(x, pos)
+    return x + pos.to(x.dtype)
+
+
 # -------------------------------------------------------- sync batch norm ---
 
 def _gather_rows(row, group, native):

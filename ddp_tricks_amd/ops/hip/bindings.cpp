@@ -258,6 +258,15 @@ at::Tensor lscale_fwd(at::Tensor u, at::Tensor gamma, at::Tensor resid);
 std::tuple<at::Tensor, at::Tensor> lscale_bwd(at::Tensor dy, at::Tensor u,
                                               at::Tensor gamma, long blocks);
 
+// attn.hip
+std::tuple<at::Tensor, at::Tensor> attn_fwd(at::Tensor qkv, long heads,
+                                            bool save);
+at::Tensor attn_bwd(at::Tensor qkv, at::Tensor o, at::Tensor lse,
+                    at::Tensor dO, long heads);
+std::tuple<long, long, long, long, long> attn_plan(const std::string& op,
+                                                   long N, long heads, long L);
+at::Tensor add_pos_fwd(at::Tensor x, at::Tensor pos);
+
 // data.hip
 std::vector<at::Tensor> batch_gather_aug(at::Tensor store, at::Tensor labels,
                                          at::Tensor index, at::Tensor lut,
@@ -619,6 +628,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "(du, dgamma) of the layer scale; the residual's gradient is dy",
           py::arg("dy"), py::arg("u"), py::arg("gamma"),
           py::arg("blocks") = -1);
+    m.def("attn_fwd", &attn_fwd,
+          "softmax(q k^T / 8) v per head of 64 channels over packed bf16 "
+          "channels_last qkv [N, 3*64*heads, H, W]: (o [N, 64*heads, H, W], "
+          "lse [N, heads, H*W] fp32); lse is empty without save",
+          py::arg("qkv"), py::arg("heads"), py::arg("save"));
+    m.def("attn_bwd", &attn_bwd,
+          "dqkv in qkv's packed layout from the forward's o and lse",
+          py::arg("qkv"), py::arg("o"), py::arg("lse"), py::arg("do"),
+          py::arg("heads"));
+    m.def("attn_plan", &attn_plan,
+          "(rows per block tile, streamed tile rows, grid.x, grid.y, grid.z) "
+          "of op 'fwd', 'bwd_dq' or 'bwd_dkv'; launches nothing",
+          py::arg("op"), py::arg("N"), py::arg("heads"), py::arg("L"));
+    m.def("add_pos_fwd", &add_pos_fwd,
+          "x + pos, pos [1, C, H, W] broadcast over N, bf16 channels_last",
+          py::arg("x"), py::arg("pos"));
     m.def("conv2d_kloop_plan", &conv2d_kloop_plan,
           "'walk' or 'decode': the K loop conv2d_fwd[_stats] (mode 0) or "
           "conv2d_dgrad (mode 1) would run for this shape; kwalk -1 "

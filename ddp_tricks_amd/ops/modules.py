@@ -190,6 +190,59 @@ class LayerScale(nn.Module):
         return F_ops.layer_scale(u, self.gamma, residual)
 
 
+class Attention2d(nn.Module):
+    """Multi-head self-attention over the H * W tokens of an [N, dim, H, W]
+    activation, head dimension 64: ``qkv`` and ``proj`` are 1x1 convs on the
+    MFMA implicit GEMM, so the packed qkv matrix the attention kernels of
+    ops/hip/attn.hip read is the qkv conv's output as it lies."""
+
+    def __init__(self, dim: int, num_heads: int):
+        super().__init__()
+        if dim != F_ops.ATTN_HEAD_DIM * num_heads:
+            raise ValueError(f"Attention2d: dim {dim} with {num_heads} heads "
+                             f"is not supported; {F_ops.ATTN_SCOPE}")
+        self.num_heads = num_heads
+        self.qkv = Conv2d(dim, 3 * dim, 1)
+        self.proj = Conv2d(dim, dim, 1)
+
+    def forward(self, x):
+        return self.proj(F_ops.attention2d(self.qkv(x), self.num_heads))
+
+
+def sincos_pos_embed(dim: int, H: int, W: int, temperature: float = 10000.0):
+    """Fixed 2-D sin-cos table [1, dim, H, W] of "Better plain ViT baselines":
+    with omega_i = temperature^(-i / (dim/4 - 1)), i < dim/4, the channels of
+    token (y, x) are [sin(x omega), cos(x omega), sin(y omega), cos(y omega)]."""
+    if dim % 4 != 0 or dim < 8:
+        raise ValueError(f"sincos_pos_embed: dim {dim} must be a multiple of 4,"
+                         " at least 8")
+    n = dim // 4
+    omega = temperature ** (-torch.arange(n, dtype=torch.float64) / (n - 1))
+    y, x = torch.meshgrid(torch.arange(H, dtype=torch.float64),
+                          torch.arange(W, dtype=torch.float64), indexing="ij")
+    ax, ay = x[..., None] * omega, y[..., None] * omega       # [H, W, n]
+    pe = torch.cat([ax.sin(), ax.cos(), ay.sin(), ay.cos()], dim=-1)
+    return pe.permute(2, 0, 1)[None].float()
+
+
+class PosEmbed2d(nn.Module):
+    """Adds the fixed sin-cos table to an [N, dim, H, W] token grid.  The table
+    is a non-persistent buffer built for (H, W) and rebuilt when the input's
+    grid differs."""
+
+    def __init__(self, dim: int, H: int, W: int):
+        super().__init__()
+        self.dim = dim
+        self.register_buffer("pos", sincos_pos_embed(dim, H, W),
+                             persistent=False)
+
+    def forward(self, x):
+        if x.shape[2:] != self.pos.shape[2:]:
+            self.pos = sincos_pos_embed(self.dim, x.shape[2],
+                                        x.shape[3]).to(self.pos.device)
+        return F_ops.add_pos(x, self.pos)
+
+
 class ReLU(nn.ReLU):
     def forward(self, x):
         return F_ops.relu(x, inplace=self.inplace)

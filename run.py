@@ -44,7 +44,8 @@ def parse_args():
                              "resnet34, resnet50, resnext50_32x4d, "
                              "resnext101_32x8d, se_resnet50, "
                              "se_resnext50_32x4d, mobilenet_v1, "
-                             "mnasnet1_0, convnext_tiny)")
+                             "mnasnet1_0, convnext_tiny, vit_tiny, "
+                             "vit_small)")
     parser.add_argument("--dataset", default="mnist", type=str,
                         help="dataset registry name (mnist, cifar10, "
                              "imagenet_synthetic)")

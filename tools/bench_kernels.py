@@ -15,6 +15,7 @@ Usage (on a GPU box):  python tools/bench_kernels.py [--resnet]
                        python tools/bench_kernels.py --gconv
                        python tools/bench_kernels.py --gn | --se
                        python tools/bench_kernels.py --ln [--blocks 512,4096]
+                       python tools/bench_kernels.py --attn
 
 Times conv fwd/dgrad/wgrad per shape with HIP events (200 reps after 20
 warmup) and prints achieved TFLOP/s next to microseconds, so kernel A/B
@@ -1277,8 +1278,92 @@ def bench_ln(rounds, blocks):
         torch.cuda.empty_cache()
 
 
+def bench_attn(rounds):
+    """Attention forward, forward with lse saved, and backward (both kernels)
+    of attn.hip at B = 256, heads 3 / 6 / 12, L = 64 / 196, against torch's
+    F.scaled_dot_product_attention and its autograd on bf16 [N, heads, L, 64]
+    tensors that torch is handed already permuted.  Alternated in one process,
+    30 warm-up calls, device events around 10 calls.  Each row: median us
+    (min-max), torch's median and its ratio to ours, achieved TFLOP/s (forward
+    4 N heads L^2 64, backward the 7 tile GEMMs run: 14 N heads L^2 64) and the
+    share of the HBM time of qkv + o (backward: qkv, o, do, dqkv) at 8 TB/s.
+    Outputs are first compared with the fp32 formulas."""
+    ext = load_extension(required=True)
+    dev = torch.device("cuda:0")
+    Fn = torch.nn.functional
+    N = 256
+    print(f"{'heads':>5s} {'L':>4s} {'op':9s} {'med us':>8s} {'min':>8s} "
+          f"{'max':>8s} {'torch us':>9s} {'torch/ours':>10s} {'TFLOP/s':>8s} "
+          f"{'%HBM':>6s}")
+
+    def check(name, a, b):
+        tol = 2.0 ** -7 * b.abs() + 2.0 ** -8 * b.abs().max()
+        if not bool(((a.float() - b).abs() <= tol).all()):
+            raise RuntimeError(f"attn {name} differs from the fp32 reference: "
+                               f"largest error {(a.float() - b).abs().max():.3g}")
+
+    def heads_view(t, h):
+        n, _, hh, ww = t.shape
+        return t.permute(0, 2, 3, 1).reshape(n, hh * ww, h, 64).transpose(1, 2)
+
+    for h in (3, 6, 12):
+        for H in (8, 14):
+            L, D = H * H, 64 * h
+            g = torch.Generator(device=dev).manual_seed(h + H)
+            qkv = (torch.randn(N, 3 * D, H, H, device=dev, generator=g)
+                   .to(torch.bfloat16).contiguous(memory_format=CL))
+            do = (torch.randn(N, D, H, H, device=dev, generator=g)
+                  .to(torch.bfloat16).contiguous(memory_format=CL))
+            qt, kt, vt = (heads_view(t, h).contiguous().requires_grad_(True)
+                          for t in qkv.chunk(3, 1))
+            dot = heads_view(do, h).contiguous()
+            ot = Fn.scaled_dot_product_attention(qt, kt, vt)
+
+            qf, kf, vf = (t.detach().float().requires_grad_(True)
+                          for t in (qt, kt, vt))
+            of = torch.softmax(qf @ kf.mT * 0.125, -1) @ vf
+            refs = torch.autograd.grad(of, [qf, kf, vf], dot.float())
+            o, lse = ext.attn_fwd(qkv, h, True)
+            dqkv = ext.attn_bwd(qkv, o, lse, do, h)
+            check("o", heads_view(o, h), of.detach())
+            for name, got, ref in zip(("dq", "dk", "dv"), dqkv.chunk(3, 1),
+                                      refs):
+                check(name, heads_view(got, h), ref)
+            del qf, kf, vf, of, refs, dqkv
+
+            gemm = 2.0 * N * h * L * L * 64
+            io = (qkv.numel() + o.numel()) * 2
+
+            def row(name, ours, theirs, flops, traffic):
+                res = _time_alternating({"ours": ours, "torch": theirs},
+                                        rounds=rounds, warmup=30)
+                med, lo, hi = res["ours"]
+                tm = res["torch"][0]
+                print(f"{h:5d} {L:4d} {name:9s} {med:8.1f} {lo:8.1f} "
+                      f"{hi:8.1f} {tm:9.1f} {tm / med:10.2f} "
+                      f"{flops / med / 1e6:8.1f} "
+                      f"{traffic / HBM_PEAK * 1e6 / med * 100:6.1f}",
+                      flush=True)
+
+            def torch_fwd():
+                with torch.no_grad():
+                    return Fn.scaled_dot_product_attention(qt, kt, vt)
+            row("fwd", lambda: ext.attn_fwd(qkv, h, False), torch_fwd,
+                2 * gemm, io)
+            row("fwd save", lambda: ext.attn_fwd(qkv, h, True),
+                lambda: Fn.scaled_dot_product_attention(qt, kt, vt),
+                2 * gemm, io)
+            row("bwd", lambda: ext.attn_bwd(qkv, o, lse, do, h),
+                lambda: torch.autograd.grad(ot, [qt, kt, vt], dot,
+                                            retain_graph=True),
+                7 * gemm, 2 * io)
+            del qkv, do, qt, kt, vt, dot, ot, o, lse
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--attn", action="store_true")
     ap.add_argument("--ln", action="store_true")
     ap.add_argument("--blocks", default="",
                     help="further forced grids for --ln's LayerNorm rows, "
@@ -1316,6 +1401,9 @@ def main():
     ap.add_argument("--bnpool", action="store_true")
     ap.add_argument("--reps", type=int, default=200)
     args = ap.parse_args()
+    if args.attn:
+        bench_attn(rounds=30)
+        return
     if args.ln:
         bench_ln(rounds=30,
                  blocks=[int(t) for t in args.blocks.split(",") if t])
